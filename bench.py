@@ -50,6 +50,26 @@ from benchlib.configs import tol_setup, run_config, polish_leg, other_configs, P
 from benchlib.multi import GATHER_LIMIT_S, guarded_gather, leave_after_stuck_gather, relaunch, dry_run, main_c5  # noqa: F401
 
 
+DUMP_SAMPLE = 2048      # instances; C2 carries ~1,600 doubles of solution each, so the files stay near 26 MB (limit 64 MB)
+
+
+def dump_outputs(gb, N, out_dir):
+    """What a caller of the timed solve receives -- the getters' x, u, pi, lam, t of every stage (concatenated over the stages,
+    one row per instance) and the per-instance iter / status -- for a fixed, seeded sample of the batch, as <out_dir>/<name>.npy
+    (float64); `instances.npy` holds the batch indices of the rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = gb.n_batch
+    idx = np.sort(np.random.default_rng(0).choice(B, min(B, DUMP_SAMPLE), replace=False))
+    arrays = {"instances": idx.astype(np.float64)}
+    for f, stages in (("x", N + 1), ("u", N), ("pi", N), ("lam", N + 1), ("t", N + 1)):
+        arrays[f] = np.concatenate([gb.get(f, k)[idx] for k in range(stages)], axis=1)
+    for f in ("iter", "status"):
+        arrays[f] = gb.info(f)[idx].astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -76,6 +96,9 @@ def main():
     ap.add_argument("--c5-total", type=int, default=524288)
     ap.add_argument("--detail-file", default=None,
                     help="where the full result object goes (default gpurun_out/bench_detail.json); stdout's last line is the compact one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (x, u, pi, lam, t per stage, iter, status) of a fixed, "
+                         "seeded sample of instances as DIR/<name>.npy in float64, to compare two builds output for output (c2, rank 0)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch path only: every rank joins a gloo group, reports the instance ranges it would own, rank 0 prints one JSON "
                          "line; no GPU is touched (the CPU tier checks that --gpus N starts N ranks)")
@@ -90,6 +113,8 @@ def main():
     if args.dry_run:
         return dry_run(args)
     if args.config == "c5":
+        if args.dump_outputs:
+            ap.error("--dump-outputs is for the c2 workload")
         return main_c5(args)
 
     import torch
@@ -142,6 +167,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gb.opts_set("profile", 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(gb, N, args.dump_outputs)
 
     from acados_amd.sharding import gather_solutions, reduce_max
     elapsed = reduce_max(elapsed, dist, dev)      # MAX over ranks

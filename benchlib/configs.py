@@ -299,10 +299,10 @@ def boundary_c3(n=4096, reps=4, larger=16384):
     registered memory), condensing + IPM + expansion on the device, one copy back, host threads write every qp_out.  `at_<larger>`: the
     same at the second size the review asked for.
     What a user of `_acados_batch_solve` gets per call, PCIe included.  The binary is built by
-    integration/Makefile where the reference tree exists and travels with the snapshot."""
-    exe = os.path.join(ROOT, "integration", "_ref_build", "ref_xcond_driver")
+    build() where the reference tree exists (oracle/Makefile, target ref) and travels with the tree."""
+    exe = os.path.join(ROOT, "oracle", "_ref", "ref_xcond_driver")
     if not os.path.exists(exe):
-        return {"skipped": "integration/_ref_build/ref_xcond_driver not built (needs the reference tree at build time)"}
+        return {"skipped": "oracle/_ref/ref_xcond_driver not built (needs the reference tree at build time)"}
     import tempfile
     from acados_amd.generators import lqr_dims, lqr_instance_qp, random_lqr_batch
     N = 50

@@ -333,7 +333,7 @@ def main():
         for rel in EDITS:
             for root in (a, b):
                 os.makedirs(os.path.dirname(os.path.join(root, rel)), exist_ok=True)
-                shutil.copy(os.path.join(REF, rel), os.path.join(root, rel))
+                shutil.copyfile(os.path.join(REF, rel), os.path.join(root, rel))     # (not the mode: the reference may be read-only)
             txt = open(os.path.join(b, rel)).read()
             for old, new in EDITS[rel]:
                 if old not in txt:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A PATCHED COPY of the reference files integration/acados.patch touches (plus the three plugin files dropped into acados/ocp_qp/),
-for the builds that compile the patched reference sources (integration/Makefile: _ref_build/acados_c_driver;
-tests/test_patched_acados_c_layer.py).  Nothing of it is stored in this repository.
+for the builds that compile the patched reference sources (oracle/Makefile, target ref: _ref/acados_c_driver and
+_ref/lockstep_driver).  Nothing of it is stored in this repository.
 
     python integration/patched_copy.py <reference tree> <destination directory>
 """

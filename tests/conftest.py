@@ -12,6 +12,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")
 
 
 # The library picks the kernel family by stage-block size AND batch size (small batches go to the
@@ -43,6 +44,22 @@ def gpu_lib():
     """the product library (hipcc, gfx950); tests using it are marked gpu"""
     from acados_amd import _lib
     return _lib.lib()
+
+
+def ref_binary(name, libpath):
+    """oracle/_ref/<name>: a driver compiled from the reference's own acados sources around this repository's plugin files, built by
+    __graft_entry__.build() where a reference tree exists (oracle/Makefile, target ref) and linked against the product library
+    (<name>) or the host-simulation library (<name>_hostsim).  The tests never read the reference tree themselves."""
+    from hostsim.build import SO
+    if os.path.realpath(libpath) == os.path.realpath(os.path.join(ROOT, "acados_amd", "csrc", "libacados_amd_qp.so")):
+        exe = os.path.join(REF_BIN, name)
+    elif os.path.realpath(libpath) == os.path.realpath(SO):
+        exe = os.path.join(REF_BIN, name + "_hostsim")
+    else:
+        pytest.skip(f"oracle/_ref/{name} is linked against the built libraries, not {libpath}")
+    if not os.path.exists(exe):
+        pytest.skip(f"{os.path.relpath(exe, ROOT)} not built: build() found no reference tree")
+    return exe
 
 
 def load_qp(rel):

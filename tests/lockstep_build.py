@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """TEST INFRASTRUCTURE -- builds tests/mock_acados/lockstep_driver.c: the reference's OWN ocp_nlp stack (SQP_RTI with
 integration/acados.patch applied, LINEAR_LS, DISCRETE_MODEL, BGH, NO_REGULARIZE, FIXED_STEP, the acados_c layer) compiled from
-/root/reference against the HPIPM / BLASFEO stand-ins of tests/mock_hpipm, around this repository's two plugin files, linked against
+the reference tree against the HPIPM / BLASFEO stand-ins of tests/mock_hpipm, around this repository's two plugin files, linked against
 the library given.  The two batch functions of the generated solver are cut out of the PATCHED template
 (c_templates_tera/acados_solver.in.c) into lockstep_batch_fns.inc with `{{ name }}` -> mpc.  Nothing of the reference is stored in
-this repository; the binary for the GPU tier is built by integration/Makefile (_ref_build/lockstep_driver) where the reference exists.
+this repository; oracle/Makefile (target ref) builds oracle/_ref/lockstep_driver and _hostsim with it where the reference exists.
 
-    python tests/lockstep_build.py <libacados_amd_qp.so | hostsim library> <output binary> [reference tree]
+    python tests/lockstep_build.py <libacados_amd_qp.so | hostsim library> <output binary> <reference tree>
 """
 import os
 import subprocess
@@ -36,7 +36,7 @@ def batch_functions(template):
     return "\n".join(out)
 
 
-def build(libpath, exe, ref="/root/reference"):
+def build(libpath, exe, ref):
     sys.path.insert(0, os.path.join(ROOT, "integration"))
     from patched_copy import patched_copy
     libdir, libname = os.path.dirname(os.path.abspath(libpath)), os.path.basename(libpath)
@@ -50,7 +50,7 @@ def build(libpath, exe, ref="/root/reference"):
                "-I", mock, os.path.join(mock, "lockstep_driver.c"), os.path.join(mock, "nlp_stubs.c"),
                os.path.join(ROOT, "tests", "mock_hpipm", "mock_hpipm.c"), os.path.join(ROOT, "tests", "mock_hpipm", "mock_blasfeo_nlp.c")] + \
               [os.path.join(pat, f) for f in PATCHED_SOURCES] + [os.path.join(ref, f) for f in REF_SOURCES] + \
-              ["-o", exe, "-L", libdir, "-l:" + libname, "-Wl,-rpath," + ("$ORIGIN/../../acados_amd/csrc" if libname == "libacados_amd_qp.so" else libdir),
+              ["-o", exe, "-L", libdir, "-l:" + libname, "-Wl,-rpath,$ORIGIN/" + os.path.relpath(libdir, os.path.dirname(os.path.abspath(exe))),
                "-Wl,-rpath-link,/opt/rocm/lib", "-Wl,--allow-shlib-undefined", "-lm", "-lpthread"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
@@ -59,5 +59,5 @@ def build(libpath, exe, ref="/root/reference"):
 
 
 if __name__ == "__main__":
-    build(sys.argv[1], sys.argv[2], *(sys.argv[3:4]))
+    build(sys.argv[1], sys.argv[2], sys.argv[3])
     print("built", sys.argv[2])

@@ -15,22 +15,20 @@ Five RTI steps in closed loop (x0 := x1 of the step).  Asserted: the option stri
 routed to the QP solver and ended in exit(1)); lock-step == per-capsule loop on the twins; the first step of sampled capsules equals
 the oracle's solution of the MPC QP written down independently in Python.
 
-CPU tier: hostsim library, a handful of capsules.  GPU tier: the binary integration/Makefile prebuilt (1,024 capsules)."""
+CPU tier: hostsim library, a handful of capsules.  GPU tier: product library (1,024 capsules).  Both drivers are built by build()
+(oracle/Makefile, target ref: oracle/_ref/lockstep_driver[_hostsim])."""
 import os
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, ref_binary
 from oracle.oracle import OracleQp, default_opts
 
 REFERENCE = "/root/reference"
-PREBUILT = os.path.join(ROOT, "integration", "_ref_build", "lockstep_driver")
 TIERS = [pytest.param("hostsim", id="hostsim"), pytest.param("gpu", id="gpu", marks=pytest.mark.gpu)]
-_BUILT = {}
 
 
 @pytest.fixture
@@ -39,18 +37,7 @@ def clib(request):
 
 
 def _exe(libpath):
-    if libpath in _BUILT:
-        return _BUILT[libpath]
-    if not os.path.isdir(os.path.join(REFERENCE, "acados", "ocp_nlp")):
-        if os.path.basename(libpath) == "libacados_amd_qp.so" and os.path.exists(PREBUILT):
-            _BUILT[libpath] = PREBUILT
-            return PREBUILT
-        pytest.skip("no reference tree and no prebuilt driver for this library")
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from lockstep_build import build
-    exe = os.path.join(tempfile.mkdtemp(prefix="lockstep_"), "lockstep_driver")
-    _BUILT[libpath] = build(libpath, exe, REFERENCE)
-    return exe
+    return ref_binary("lockstep_driver", libpath)
 
 
 def _model(N, n, seed):

@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_qp
+from conftest import ROOT, load_qp, ref_binary
 from oracle.oracle import OracleQp, default_opts
 
 TIERS = [pytest.param("hostsim", id="hostsim"), pytest.param("gpu", id="gpu", marks=pytest.mark.gpu)]
@@ -22,26 +22,16 @@ def clib(request):
     return request.getfixturevalue("hostsim_lib" if request.param == "hostsim" else "gpu_lib")
 
 
-REFERENCE = "/root/reference"
-PREBUILT = os.path.join(ROOT, "integration", "_ref_build", "mock_acados_driver")    # integration/Makefile, built by __graft_entry__.build()
-
-
 def _build(libpath, tmp_path, headers="restated"):
     """headers = "restated": the acados declarations restated under tests/mock_acados/include (runs everywhere);
-    headers = "reference": acados/ocp_qp/ocp_qp_common.h and acados/utils/types.h are the REFERENCE'S OWN files (-I /root/reference),
-    only hpipm/include/*.h and blasfeo/include/*.h (empty submodules there) are stand-ins (tests/mock_hpipm).  /root/reference
-    does not exist on the GPU box: there the binary built from the same sources in the build container (integration/Makefile,
-    linked against the product library) is run."""
+    headers = "reference": acados/ocp_qp/ocp_qp_common.h and acados/utils/types.h are the REFERENCE'S OWN files, only
+    hpipm/include/*.h and blasfeo/include/*.h (empty submodules there) are stand-ins (tests/mock_hpipm): the same sources built by
+    build() into oracle/_ref/mock_acados_driver[_hostsim] (oracle/Makefile, target ref)."""
+    if headers == "reference":
+        return ref_binary("mock_acados_driver", libpath)
     exe = str(tmp_path / "mock_acados_driver")
     libdir, libname = os.path.dirname(libpath), os.path.basename(libpath)
-    if headers == "reference":
-        if not os.path.isdir(os.path.join(REFERENCE, "acados", "ocp_qp")):
-            if libname == "libacados_amd_qp.so" and os.path.exists(PREBUILT):
-                return PREBUILT
-            pytest.skip("no reference tree and no prebuilt reference-header driver for this library")
-        inc = ["-I", REFERENCE, "-I", os.path.join(ROOT, "tests", "mock_hpipm"), "-I", MOCK]
-    else:
-        inc = ["-I", os.path.join(MOCK, "include")]
+    inc = ["-I", os.path.join(MOCK, "include")]
     cmd = ["gcc", "-std=gnu11", "-O2", "-fopenmp", "-Wall", "-Wno-unused-parameter"] + inc + ["-I", os.path.join(ROOT, "include"),
            os.path.join(MOCK, "driver.c"), os.path.join(ROOT, "integration", "ocp_qp_gpu_ipm.c"), "-o", exe,
            "-L", libdir, "-l:" + libname, "-Wl,-rpath," + libdir, "-lm", "-lpthread"]

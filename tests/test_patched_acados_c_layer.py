@@ -7,23 +7,19 @@ REQUIRE(status == 0); REQUIRE(max KKT residual <= tol) through ocp_qp_inf_norm_r
 device condensing module on acados' types (ocp_qp_gpu_pcond.c); the patched ocp_qp_xcond_solver.c releases the module's device batch
 in `terminate`.  HPIPM / BLASFEO: the stand-ins of tests/mock_hpipm.
 
-CPU tier: built here from a patched copy of the reference files, linked against the host-simulation library.  GPU tier: the binary
-built in the build container against the product library (integration/Makefile: _ref_build/acados_c_driver)."""
+Both tiers run the drivers build() compiled from a patched copy of the reference files (oracle/Makefile, target ref):
+oracle/_ref/acados_c_driver_hostsim (CPU tier, host-simulation library) and oracle/_ref/acados_c_driver (GPU tier, product library)."""
 import os
 import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_qp
+from conftest import ROOT, load_qp, ref_binary
 from oracle.oracle import OracleQp, default_opts
-from test_mock_acados import MOCK, REFERENCE, _write_qp
+from test_mock_acados import _write_qp
 
 TIERS = [pytest.param("hostsim", id="hostsim"), pytest.param("gpu", id="gpu", marks=pytest.mark.gpu)]
-PREBUILT = os.path.join(ROOT, "integration", "_ref_build", "acados_c_driver")
-_BUILT = {}
 
 
 @pytest.fixture
@@ -32,32 +28,7 @@ def clib(request):
 
 
 def _build(libpath):
-    if libpath in _BUILT:
-        return _BUILT[libpath]
-    libdir, libname = os.path.dirname(libpath), os.path.basename(libpath)
-    if not os.path.isdir(os.path.join(REFERENCE, "acados", "ocp_qp")):
-        if libname == "libacados_amd_qp.so" and os.path.exists(PREBUILT):
-            _BUILT[libpath] = PREBUILT
-            return PREBUILT
-        pytest.skip("no reference tree and no prebuilt driver for this library")
-    sys.path.insert(0, os.path.join(ROOT, "integration"))
-    from patched_copy import patched_copy
-    tmp = tempfile.mkdtemp(prefix="acados_c_")
-    pat = patched_copy(REFERENCE, os.path.join(tmp, "patched"))
-    exe = os.path.join(tmp, "acados_c_driver")
-    cmd = ["gcc", "-std=gnu11", "-O2", "-fopenmp", "-Wall", "-Wno-unused-parameter", "-Wno-unused-function", "-Wno-implicit-function-declaration",
-           "-DACADOS_WITH_GPU_IPM", "-I", pat, "-I", os.path.join(pat, "interfaces"), "-I", REFERENCE, "-I", os.path.join(REFERENCE, "interfaces"),
-           "-I", os.path.join(ROOT, "tests", "mock_hpipm"), "-I", os.path.join(ROOT, "include"), "-I", MOCK,
-           os.path.join(MOCK, "acados_c_driver.c"), os.path.join(MOCK, "acados_c_stubs.c"),
-           os.path.join(pat, "interfaces", "acados_c", "ocp_qp_interface.c"), os.path.join(pat, "acados", "ocp_qp", "ocp_qp_xcond_solver.c"),
-           os.path.join(pat, "acados", "ocp_qp", "ocp_qp_gpu_ipm.c"), os.path.join(pat, "acados", "ocp_qp", "ocp_qp_gpu_pcond.c"),
-           os.path.join(ROOT, "tests", "mock_hpipm", "mock_hpipm.c")] + \
-          [os.path.join(REFERENCE, f) for f in ("acados/ocp_qp/ocp_qp_common.c", "acados/utils/mem.c", "acados/utils/timing.c")] + \
-          ["-o", exe, "-L", libdir, "-l:" + libname, "-Wl,-rpath," + libdir, "-lm", "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    _BUILT[libpath] = exe
-    return exe
+    return ref_binary("acados_c_driver", libpath)
 
 
 def _run(exe, qp, tmp_path, n2s, by_name=False):

@@ -11,21 +11,19 @@ The solution is compared with the oracle, the plugin's t with the reference's ow
 entry must report <= 1e-8, forward sensitivities through the reference's eval_forw_sens against a dense KKT solve, and a
 1,024-capsule C3-shaped batch (N = 50 -> N2 = 10) goes through ocp_qp_gpu_xcond_solver_acados_evaluate_batch (fused on the device).
 
-CPU tier: linked against the host-simulation library, built here.  GPU tier: /root/reference does not exist on the GPU box --
-the binary built in the build container against the product library (integration/Makefile) is run."""
+Both tiers run the drivers build() compiled from the reference (oracle/Makefile, target ref): oracle/_ref/ref_xcond_driver_hostsim
+(CPU tier, host-simulation library) and oracle/_ref/ref_xcond_driver (GPU tier, product library)."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_qp
+from conftest import ROOT, load_qp, ref_binary
 from oracle.oracle import OracleQp, default_opts
-from test_mock_acados import MOCK, REFERENCE, _check_sens_vs_dense, _perturbed, _seeds, _split_bin, _write_qp
+from test_mock_acados import _check_sens_vs_dense, _perturbed, _seeds, _split_bin, _write_qp
 
 TIERS = [pytest.param("hostsim", id="hostsim"), pytest.param("gpu", id="gpu", marks=pytest.mark.gpu)]
-PREBUILT = os.path.join(ROOT, "integration", "_ref_build", "ref_xcond_driver")
-REF_SOURCES = ["acados/ocp_qp/ocp_qp_xcond_solver.c", "acados/ocp_qp/ocp_qp_common.c", "acados/utils/mem.c", "acados/utils/timing.c"]
 
 
 @pytest.fixture
@@ -33,33 +31,8 @@ def clib(request):
     return request.getfixturevalue("hostsim_lib" if request.param == "hostsim" else "gpu_lib")
 
 
-_BUILT = {}
-
-
 def _build(libpath, tmp_path):
-    if libpath not in _BUILT:
-        _BUILT[libpath] = _build_once(libpath, tmp_path)
-    return _BUILT[libpath]
-
-
-def _build_once(libpath, tmp_path):
-    libdir, libname = os.path.dirname(libpath), os.path.basename(libpath)
-    if not os.path.isdir(os.path.join(REFERENCE, "acados", "ocp_qp")):
-        if libname == "libacados_amd_qp.so" and os.path.exists(PREBUILT):
-            return PREBUILT
-        pytest.skip("no reference tree and no prebuilt driver for this library")
-    import tempfile
-    exe = os.path.join(tempfile.mkdtemp(prefix="ref_xcond_"), "ref_xcond_driver")
-    cmd = ["gcc", "-std=gnu11", "-O2", "-fopenmp", "-Wall", "-Wno-unused-parameter", "-I", REFERENCE, "-I", os.path.join(ROOT, "tests", "mock_hpipm"),
-           "-I", os.path.join(ROOT, "include"), "-I", MOCK,
-           "-I", os.path.join(ROOT, "integration"),
-           os.path.join(MOCK, "ref_xcond_driver.c"), os.path.join(MOCK, "copy_xcond.c"), os.path.join(ROOT, "integration", "ocp_qp_gpu_ipm.c"),
-           os.path.join(ROOT, "integration", "ocp_qp_gpu_pcond.c"),
-           os.path.join(ROOT, "tests", "mock_hpipm", "mock_hpipm.c")] + [os.path.join(REFERENCE, f) for f in REF_SOURCES] + \
-          ["-o", exe, "-L", libdir, "-l:" + libname, "-Wl,-rpath," + libdir, "-lm", "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return ref_binary("ref_xcond_driver", libpath)
 
 
 def _run(exe, qp, tmp_path, flags):
