@@ -233,6 +233,22 @@ struct ocp_qp_gpu_batch
     GArr sfix = {nullptr, 0, 0};         /* derivative of the equality-flagged variables (e.g. x0), [N+2][n] */
     int *d_saved_status = nullptr;
     ocp_qp_gpu_batch *sens_child = nullptr; /* wave-per-instance sub-batch the sensitivities of a one-instance-per-lane batch run in */
+    /* Riccati recursion (option "ric_alg"): 1 square-root (every family), 0 classical (wave-per-instance sweeps only, RIC0 of
+     * ipm_kernels_wpi.hpp).  A wave-per-instance-layout batch swaps its kernel set in place (ric1 keeps what it replaced); a
+     * one-instance-per-lane batch hands every solve to ric0_child, a wave-per-instance batch at its padded dims */
+    int ric_alg = 1;
+    struct Ric1
+    {
+        bool saved = false;
+        KernelSet own_ks;
+        int w16 = 0;
+        kern_redo_t w16_solve = nullptr;
+        bool wpi_mfma = false;
+        size_t shmem = 0, shmem_fwd = 0, shmem_fact = 0;
+        std::string kname;
+    } ric1;
+    ocp_qp_gpu_batch *ric0_child = nullptr;
+    int *d_rlist = nullptr; /* 0 .. B-1: the hand-over list of ric0_child */
     int *d_slist = nullptr;
     int sens_cap = 0;
     int tail_cap = 0;
@@ -318,9 +334,87 @@ int padded_var(const ocp_qp_gpu_batch *b, int k, int iv)
     return iv < b->nu[k] ? iv : b->ks->NU + (iv - b->nu[k]);
 }
 
+/* the classical Riccati kernel set of the wave-per-instance family at padded dims (wx, wu) */
+KernelSet wpi_ric0_set(int wx, int wu, int mg, int ms)
+{
+    const bool gen = mg > 0 || ms > 0;
+    static const kern_redo_t fact_box[8] = {gqp::kw_factor<1, false, 0, 0, true>, gqp::kw_factor<2, false, 0, 0, true>,
+                                            gqp::kw_factor<3, false, 0, 0, true>, gqp::kw_factor<4, false, 0, 0, true>,
+                                            gqp::kw_factor<5, false, 0, 0, true>, gqp::kw_factor<6, false, 0, 0, true>,
+                                            gqp::kw_factor<7, false, 0, 0, true>, gqp::kw_factor<8, false, 0, 0, true>};
+    static const kern_redo_t fact_gen[8] = {gqp::kw_factor<1, true, 0, 0, true>, gqp::kw_factor<2, true, 0, 0, true>,
+                                            gqp::kw_factor<3, true, 0, 0, true>, gqp::kw_factor<4, true, 0, 0, true>,
+                                            gqp::kw_factor<5, true, 0, 0, true>, gqp::kw_factor<6, true, 0, 0, true>,
+                                            gqp::kw_factor<7, true, 0, 0, true>, gqp::kw_factor<8, true, 0, 0, true>};
+    const int t8 = (wx + wu + 7) / 8 - 1;
+    const kern_redo_t fact = gen ? fact_gen[t8] : fact_box[t8];
+    const kern_redo_t rhs = gen ? gqp::kw_backrhs<true, 0, 0, true> : gqp::kw_backrhs<false, 0, 0, true>;
+    const kern_redo_t faff = gen ? gqp::kw_fwd<false, true, 0, 0, true> : gqp::kw_fwd<false, false, 0, 0, true>;
+    const kern_redo_t fcor = gen ? gqp::kw_fwd<true, true, 0, 0, true> : gqp::kw_fwd<true, false, 0, 0, true>;
+    const kern_opts_t init = gen ? gqp::kw_init<true> : gqp::kw_init<false>;
+    const kern_plain_t fin = gen ? gqp::kw_finalize<true> : gqp::kw_finalize<false>;
+    return KernelSet{wx, wu, mg, ms, init, fact, rhs, faff, fcor, fin, {fact, fact}, {rhs, rhs}, {faff, faff}, {fcor, fcor}, fin};
+}
+
+/* dynamic LDS above the default limit: raise it for the four sweep kernels of the batch's own set */
+static void wpi_lds_attributes(ocp_qp_gpu_batch *b)
+{
+    if (std::max(b->shmem, b->shmem_fact) <= 64 * 1024) return;
+    const void *fns[] = {(const void *) b->own_ks.back_fact, (const void *) b->own_ks.back_rhs,
+                         (const void *) b->own_ks.fwd_aff, (const void *) b->own_ks.fwd_corr};
+    for (const void *f : fns)
+        HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int) std::max(b->shmem, b->shmem_fact)));
+}
+
+/* the kernel set, LDS sizes and name of a batch for its ric_alg (see ocp_qp_gpu_batch::ric_alg) */
+static void ric_configure(ocp_qp_gpu_batch *b)
+{
+    ocp_qp_gpu_batch::Ric1 &r = b->ric1;
+    if (b->ric_alg == 1)
+    {
+        if (!r.saved) return;
+        if (b->wpi)
+        {
+            b->own_ks = r.own_ks; b->ks = &b->own_ks;
+            b->w16 = r.w16; b->w16_solve = r.w16_solve; b->wpi_mfma = r.wpi_mfma;
+            b->shmem = r.shmem; b->shmem_fwd = r.shmem_fwd; b->shmem_fact = r.shmem_fact;
+            if (b->finalized) wpi_lds_attributes(b);
+        }
+        b->kname = r.kname;
+        r.saved = false;
+        return;
+    }
+    if (!r.saved)
+    {
+        r.own_ks = b->own_ks; r.w16 = b->w16; r.w16_solve = b->w16_solve; r.wpi_mfma = b->wpi_mfma;
+        r.shmem = b->shmem; r.shmem_fwd = b->shmem_fwd; r.shmem_fact = b->shmem_fact; r.kname = b->kname;
+        r.saved = true;
+    }
+    const int wx = b->ks->NX, wu = b->ks->NU, mg = b->ks->NG, ms = b->ks->NS;
+    const size_t con = gqp::wpi_con_doubles(wx + wu, mg, ms);
+    const size_t shmem = (gqp::wpi3_lds_doubles(wx, wu) + con) * sizeof(double);
+    const size_t shmem_fact = (gqp::wpi2_ric0_lds_doubles(wx, wu) + con) * sizeof(double);
+    if (b->wpi)
+    {
+        b->own_ks = wpi_ric0_set(wx, wu, mg, ms);
+        b->ks = &b->own_ks;
+        b->w16 = 0; b->w16_solve = nullptr; b->wpi_mfma = false;
+        b->shmem = shmem; b->shmem_fwd = (gqp::wpi3_lds_doubles(wx, wu, 1) + con) * sizeof(double); b->shmem_fact = shmem_fact;
+        if (b->finalized) wpi_lds_attributes(b);
+    }
+    char nm[160];
+    if (mg || ms) snprintf(nm, sizeof(nm), "wpi-gen(nx=%d,nu=%d,ng=%d,ns=%d,lds=%zuB,ric0)", wx, wu, mg, ms, shmem_fact);
+    else snprintf(nm, sizeof(nm), "wpi-box(nx=%d,nu=%d,lds=%zuB,ric0)", wx, wu, shmem);
+    b->kname = nm;
+}
+
 void finalize_structure(ocp_qp_gpu_batch *b)
 {
     if (b->finalized) return;
+    /* ric_alg 0 set before the structure: the checks below decide for the set ric_alg 1 runs (the sixteen-lanes soft fallback,
+     * the LDS limits); the classical set goes back on afterwards */
+    const bool ric0 = b->ric_alg == 0 && b->ric1.saved;
+    if (ric0) { b->ric_alg = 1; ric_configure(b); }
     const int N = b->N, NX = b->ks->NX, NU = b->ks->NU;
     const int n = NX + NU, NP = n * (n + 1) / 2;
     b->st.assign(N + 1, GqpStage());
@@ -417,14 +511,7 @@ void finalize_structure(ocp_qp_gpu_batch *b)
     if (b->wpi)
     {
         b->use_box = true;
-        if (std::max(b->shmem, b->shmem_fact) > 64 * 1024)
-        {
-            /* more than the default dynamic LDS limit: raise it for the four sweep kernels */
-            const void *fns[] = {(const void *) b->own_ks.back_fact, (const void *) b->own_ks.back_rhs,
-                                 (const void *) b->own_ks.fwd_aff, (const void *) b->own_ks.fwd_corr};
-            for (const void *f : fns)
-                HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int) std::max(b->shmem, b->shmem_fact)));
-        }
+        wpi_lds_attributes(b); /* more than the default dynamic LDS limit: raised for the four sweep kernels */
     }
     b->d_st = dalloc<GqpStage>(b, N + 1);
     HIPCHK(hipMemcpy(b->d_st, b->st.data(), sizeof(GqpStage) * (N + 1), hipMemcpyHostToDevice));
@@ -507,6 +594,7 @@ void finalize_structure(ocp_qp_gpu_batch *b)
     }
     HIPCHK(hipStreamSynchronize(b->stream));
     b->finalized = true;
+    if (ric0) { b->ric_alg = 0; ric_configure(b); }
 }
 
 void ensure_stat(ocp_qp_gpu_batch *b)
@@ -620,7 +708,10 @@ int field_map(ocp_qp_gpu_batch *b, const char *f, int k, std::vector<int> &map, 
     else if (!strcmp(f, "ric_L"))
     {
         /* Cholesky factor of the stage matrix of the last factorisation, variables [u;x] of this
-         * stage (padding removed), nv x nv column-major, lower triangle (upper = 0) */
+         * stage (padding removed), nv x nv column-major, lower triangle (upper = 0).
+         * ric_alg 0 (classical layout, get_int "ric_alg"), stages k >= 1: columns 0..nu-1 as above ([Lu; Lxu], the factor of
+         * R~ + B'PB and its coupling rows), the trailing x-block is the lower triangle of P_k itself; ric_l = [lu; p_k].
+         * Stage 0 is the full factor in both layouts. */
         *arr = D.Lf;
         const int nv = nu + nx;
         for (int c = 0; c < nv; c++)
@@ -980,6 +1071,7 @@ try
     if (b->compact) ocp_qp_gpu_batch_destroy(b->compact);
     if (b->tail) ocp_qp_gpu_batch_destroy(b->tail);
     if (b->sens_child) ocp_qp_gpu_batch_destroy(b->sens_child);
+    if (b->ric0_child) ocp_qp_gpu_batch_destroy(b->ric0_child);
     delete b;
 }
 catch (const gqp_hip_failure &) {}
@@ -1058,6 +1150,20 @@ try
     return rc;
 }
 catch (const gqp_hip_failure &) { return -1; }
+
+/* a new ric_alg: the sub-batches built for the old kernel set go, the factor in HBM is the old one's */
+static void ric_switch(ocp_qp_gpu_batch *b, int v)
+{
+    b->ric_alg = v;
+    if (b->compact) { ocp_qp_gpu_batch_destroy(b->compact); b->compact = nullptr; }
+    if (b->tail) { ocp_qp_gpu_batch_destroy(b->tail); b->tail = nullptr; }
+    if (b->sens_child) { ocp_qp_gpu_batch_destroy(b->sens_child); b->sens_child = nullptr; }
+    if (b->ric0_child) { ocp_qp_gpu_batch_destroy(b->ric0_child); b->ric0_child = nullptr; }
+    b->factor_stale = true;
+    b->sens_open = false;
+    if (b->child) ric_switch(b->child, v); /* the condensed batch of partial condensing */
+    ric_configure(b);
+}
 
 /* (re)create the batch's stream with a priority; the batch must be idle */
 static void set_stream_priority(ocp_qp_gpu_batch *b, int prio)
@@ -1173,7 +1279,11 @@ try
     }
     else if (!strcmp(f, "ric_alg"))
     {
-        if (*i != 1) fprintf(stderr, "acados_amd: ric_alg=%d requested, only the square-root Riccati (1) is implemented\n", *i);
+        /* acados_ocp_options.py:1084-1101: 1 square-root Riccati (the full-space stage Hessian must be positive definite), 0
+         * classical (only the reduced Hessian must be).  The same value again (the adapters resend their options before every
+         * solve) costs nothing; a change takes effect at the next solve */
+        if (*i != 0 && *i != 1) { fprintf(stderr, "acados_amd: ric_alg must be 0 or 1, got %d\n", *i); return -1; }
+        if (*i != b->ric_alg) ric_switch(b, *i);
     }
     else if (!strcmp(f, "hpipm_mode"))
     {
@@ -1331,6 +1441,7 @@ static void pcond_setup(ocp_qp_gpu_batch *b)
                                              b->B, b->device, b->ks->NX, BS * NU);
     if (c && b->stream_priority) set_stream_priority(c, b->stream_priority);
     if (!c) { decline("the condensed shape has no kernel instantiation"); return; }
+    if (b->ric_alg != c->ric_alg) ric_switch(c, b->ric_alg); /* condensing never factorises: the child's sweeps carry the choice */
     for (int j = 0; j <= N2; j++)
     {
         if (!cidxb[j].empty()) ocp_qp_gpu_batch_set_int(c, "idxb", j, cidxb[j].data(), (int) cidxb[j].size());
@@ -1870,6 +1981,92 @@ static int dense_solve(ocp_qp_gpu_batch *b)
     return bad;
 }
 
+static void refactor_at_solution(ocp_qp_gpu_batch *b);
+
+/*
+ * ric_alg 0 on a one-instance-per-lane batch: the classical sweeps exist in the wave-per-instance family only.  The whole
+ * batch (QP data, iterate, loop scalars) is copied into ric0_child -- that family at the same padded dims, the conversion of
+ * the tail switch --, solved there, and the iterate, the factor at the solution and the per-instance results come back.
+ */
+static ocp_qp_gpu_batch *ric0_copy_in(ocp_qp_gpu_batch *b)
+{
+    hipStream_t s = b->stream;
+    if (!b->ric0_child)
+    {
+        ocp_qp_gpu_batch *c = batch_create_shape(b->N, b->nx.data(), b->nu.data(), b->nbx.data(), b->nbu.data(), b->ng.data(),
+                                                 b->ns.data(), b->B, b->device, b->ks->NX, b->ks->NU, b->ks, true);
+        if (!c) { fprintf(stderr, "acados_amd: cannot create the classical-Riccati sub-batch\n"); return nullptr; }
+        if (b->stream_priority) set_stream_priority(c, b->stream_priority);
+        c->idxb = b->idxb; c->idxs_rev = b->idxs_rev; c->idxe = b->idxe; c->nbxe = b->nbxe;
+        c->ric_alg = 0;
+        ric_configure(c);
+        finalize_structure(c);
+        std::vector<int> list(b->B);
+        for (int i = 0; i < b->B; i++) list[i] = i;
+        if (!b->d_rlist) b->d_rlist = dalloc<int>(b, b->Bp);
+        HIPCHK(hipMemcpy(b->d_rlist, list.data(), sizeof(int) * b->B, hipMemcpyHostToDevice));
+        b->ric0_child = c;
+    }
+    ocp_qp_gpu_batch *c = b->ric0_child;
+    c->O = b->O;
+    c->tol_comp_soft_scale = b->tol_comp_soft_scale;
+    c->polish = b->polish; c->polish_ratio = b->polish_ratio; c->polish_min = b->polish_min;
+    c->print_level = b->print_level; c->profile = b->profile; c->compact_min = b->compact_min; c->solve_max = b->solve_max;
+    c->t0_min = b->t0_min; c->lam0_min = b->lam0_min;
+    const int cnt = b->B;
+    const dim3 block(64);
+#define GQP_COPY_IN(A) copy_level(b->D.A, c->D.A, b->d_rlist, cnt, 0, s);
+    GQP_FOR_STATE_ARRAYS(GQP_COPY_IN)
+#undef GQP_COPY_IN
+    copy_level(b->D.amask, c->D.amask, b->d_rlist, cnt, 0, s);
+    hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), block, 0, s, b->D, c->D, b->d_rlist, cnt, 0);
+    HIPCHK(hipStreamSynchronize(s)); /* the sub-batch works on its own stream */
+    return c;
+}
+
+/* the factor of ric0_child (classical layout) into the parent's Lf / lf */
+static void ric0_factor_back(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *c)
+{
+    hipStream_t s = b->stream;
+    copy_level(b->D.Lf, c->D.Lf, b->d_rlist, b->B, 1, s);
+    copy_level(b->D.lf, c->D.lf, b->d_rlist, b->B, 1, s);
+    HIPCHK(hipStreamSynchronize(s));
+    b->factor_stale = false;
+}
+
+/* the classical factor at the current iterate of a one-instance-per-lane batch (ric_alg 0): its own kernels only have the
+ * square-root layout, which the getters would read as the classical one */
+static void ric0_refactor(ocp_qp_gpu_batch *b)
+{
+    ocp_qp_gpu_batch *c = ric0_copy_in(b);
+    if (!c) throw gqp_hip_failure{-1};
+    refactor_at_solution(c);
+    ric0_factor_back(b, c);
+}
+
+static int ric0_solve(ocp_qp_gpu_batch *b)
+{
+    hipStream_t s = b->stream;
+    ocp_qp_gpu_batch *c = ric0_copy_in(b);
+    if (!c) return -1;
+    const int cnt = b->B;
+    const dim3 block(64);
+    const int bad = ocp_qp_gpu_batch_solve(c);
+    if (bad < 0) return bad;
+    if (c->factor_stale) refactor_at_solution(c);
+#define GQP_COPY_OUT(A) copy_level(b->D.A, c->D.A, b->d_rlist, cnt, 1, s);
+    GQP_FOR_RESULT_ARRAYS(GQP_COPY_OUT)
+#undef GQP_COPY_OUT
+    hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), block, 0, s, b->D, c->D, b->d_rlist, cnt, 1);
+    ric0_factor_back(b, c);
+    b->time_tot = c->time_tot; b->time_xcond = 0.0;
+    b->last_iters = c->last_iters; b->launches = c->launches;
+    b->n_compactions = c->n_compactions; b->n_tail_switches = 0; b->n_single_launch = c->n_single_launch;
+    b->n_polished = c->n_polished; b->n_polish_reverted = c->n_polish_reverted;
+    b->sens_open = false;
+    return bad;
+}
+
 int ocp_qp_gpu_batch_solve(ocp_qp_gpu_batch *b)
 try
 {
@@ -1881,6 +2078,7 @@ try
         if (b->pcond_state == 0) pcond_setup(b);
         if (b->pcond_state == 1) return pcond_solve(b, b->lhs_ready ? 2 : 3);
     }
+    if (b->ric_alg == 0 && !b->wpi) return ric0_solve(b);
     b->time_xcond = 0.0;
     ensure_stat(b);
     const KernelSet *ks = b->ks;
@@ -1957,6 +2155,7 @@ catch (const gqp_hip_failure &) { return -1; }
  * are restored. */
 static void refactor_at_solution(ocp_qp_gpu_batch *b)
 {
+    if (b->ric_alg == 0 && !b->wpi) { ric0_refactor(b); return; }
     hipStream_t s = b->stream;
     const dim3 g64((b->B + 63) / 64), blk(64);
     if (!b->d_saved_status) b->d_saved_status = dalloc<int>(b, b->Bp);
@@ -2080,6 +2279,8 @@ static void sens_solve_sliced(ocp_qp_gpu_batch *b)
         if (!c) { fprintf(stderr, "acados_amd: cannot create the sensitivity sub-batch\n"); exit(1); }
         c->idxb = b->idxb; c->idxs_rev = b->idxs_rev; c->idxe = b->idxe; c->nbxe = b->nbxe;
         c->tail_max = 0;
+        c->ric_alg = b->ric_alg; /* the factor at the solution in the layout of the batch's Riccati recursion */
+        ric_configure(c);
         finalize_structure(c);
         const int n = c->D.NX + c->D.NU;
         c->sfix = garr<double>(c, (size_t) (c->N + 2) * n);
@@ -2303,6 +2504,7 @@ try
 {
     HIPCHK(hipSetDevice(b->device));
     if (b->pcond_state == 1 && b->child) return ocp_qp_gpu_batch_get_stat(b->child, inst, stat, max_rows);
+    if (b->ric_alg == 0 && !b->wpi && b->ric0_child) return ocp_qp_gpu_batch_get_stat(b->ric0_child, inst, stat, max_rows);
     if (!b->D.stat || inst < 0 || inst >= b->stat_inst) return -1;
     const int rows = std::min(max_rows, b->stat_rows);
     std::vector<double> h((size_t) b->stat_rows * GQP_STAT_COLS * b->stat_inst);
@@ -2460,6 +2662,7 @@ int ocp_qp_gpu_batch_get_int(ocp_qp_gpu_batch *b, const char *f, int k, int *out
 {
     if (k < 0 || k > b->N) return -1;
     const std::vector<int> *v = nullptr;
+    if (!strcmp(f, "ric_alg")) { out[0] = b->ric_alg; return 1; } /* 0: Lf / lf hold the classical layout (ric_L, ric_l) */
     if (!strcmp(f, "idxb")) v = &b->idxb[k]; else if (!strcmp(f, "idxs_rev")) v = &b->idxs_rev[k]; else if (!strcmp(f, "idxe")) v = &b->idxe[k];
     if (!v) { fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_get_int: unknown field %s\n", f); return -1; }
     for (size_t e = 0; e < v->size(); e++) out[e] = (*v)[e];

@@ -798,6 +798,12 @@ __host__ __device__ static inline size_t wpi2_lds_doubles(int NX, int NU)
     const int n = NX + NU, NP = n * (n + 1) / 2, T8 = (n + 7) / 8, SX = wpi2_sx(NX);
     return (size_t) NP + 8 + (size_t) 8 * T8 * SX + (size_t) NX * SX + 6 * 64 + 2 * 72 + 64 + 8;
 }
+/* RIC0: the classical sweep keeps [B A]' and W = [B A]' P+ side by side (one more 8 T8 x SX block behind the others) */
+__host__ __device__ static inline size_t wpi2_ric0_lds_doubles(int NX, int NU)
+{
+    const int n = NX + NU, T8 = (n + 7) / 8;
+    return wpi2_lds_doubles(NX, NU) + (size_t) 8 * T8 * wpi2_sx(NX);
+}
 
 __device__ static inline WpiLds2 wpi2_carve(double *sm, int NX, int NU)
 {
@@ -815,8 +821,14 @@ __device__ static inline WpiLds2 wpi2_carve(double *sm, int NX, int NU)
 }
 
 /* CNX, CNU != 0: the state / input dimensions as COMPILE-TIME constants (the BASELINE shapes): trip counts, row strides
- * and the packed-triangle arithmetic fold; 0 = run-time dims, any shape */
-template <int T8, bool GEN, int CNX = 0, int CNU = 0>
+ * and the packed-triangle arithmetic fold; 0 = run-time dims, any shape.
+ * RIC0: the CLASSICAL Riccati recursion (ric_alg 0).  P itself is carried instead of its Cholesky factor, so only
+ * R~ + B'PB has to be positive definite, the stage blocks [R S; S' Q] may be indefinite.  Stage k >= 1:
+ *   M = H~ + [B A]' P+ [B A] with W = [B A]' P+ formed first (P+ symmetric, held in full in Lx), m = g~ + [B A]'(P+ rb + p+);
+ *   the Cholesky runs over the first NU columns only; the trailing Schur complement is P_k, its rhs entries p_k.
+ * Storage per stage: Lf = [Lu; Lxu | lower triangle of P_k], lf = [lu; p_k].  Stage 0 is factorised in full, as in the
+ * square-root form (its x-block is the reduced Hessian in x0). */
+template <int T8, bool GEN, int CNX = 0, int CNU = 0, bool RIC0 = false>
 /* T8 <= 4: keep two waves per SIMD (<= 256 VGPRs; the GEN variant sits right at the line) */
 __global__ void __launch_bounds__(64) GQP_WAVES_PER_EU(T8 <= 4 ? 2 : 1) kw_factor(GqpDev D, GqpOpts O, int redo)
 {
@@ -826,13 +838,16 @@ __global__ void __launch_bounds__(64) GQP_WAVES_PER_EU(T8 <= 4 ? 2 : 1) kw_facto
     if (inst >= D.B) return;
     if (D.status[inst] != GQP_RUNNING) return;
     const WpiLds2 L = wpi2_carve(smem, NX, NU);
-    const WpiCon C = wpi_con_carve(smem + wpi2_lds_doubles(NX, NU), n, GEN ? D.NG : 0, GEN ? D.NS : 0);
+    const WpiCon C = wpi_con_carve(smem + (RIC0 ? wpi2_ric0_lds_doubles(NX, NU) : wpi2_lds_doubles(NX, NU)), n, GEN ? D.NG : 0, GEN ? D.NS : 0);
+    double *const Wc = RIC0 ? smem + wpi2_lds_doubles(NX, NU) : nullptr; /* RIC0: W = [B A]' P+ (8 T8 x SX) */
     const int SX = L.SX, TX = (NX + 7) / 8;
     const int lr = lane >> 3, lc = lane & 7;
     const bool mine = lane < n;
 
     /* zero what is only ever partly overwritten */
     for (int e = lane; e < 8 * T8 * SX; e += 64) L.Bw[e] = 0.0;
+    if (RIC0)
+        for (int e = lane; e < 8 * T8 * SX; e += 64) Wc[e] = 0.0;
     for (int e = lane; e < NX * SX; e += 64) L.Lx[e] = 0.0;
     for (int e = lane; e < 2 * 72; e += 64) L.cb[e] = 0.0;
     L.lx[lane] = 0.0;
@@ -1065,7 +1080,7 @@ __global__ void __launch_bounds__(64) GQP_WAVES_PER_EU(T8 <= 4 ? 2 : 1) kw_facto
         if (mine) { nacc(nrm_g, gt); WAT(D.rg, k * n + lane) = gt; }
         L.gam[lane] = gam;
         GQP_TICK(5);
-        /* ---- W tiles: W = [B A]' Lx+ (Lx+ has explicit zeros above its diagonal) ---- */
+        /* ---- W tiles: W = [B A]' Lx+ (Lx+ has explicit zeros above its diagonal); RIC0: W = [B A]' P+ (P+ in full) ---- */
         double Wt[T8][T8];
 #pragma unroll
         for (int a = 0; a < T8; a++)
@@ -1085,15 +1100,16 @@ __global__ void __launch_bounds__(64) GQP_WAVES_PER_EU(T8 <= 4 ? 2 : 1) kw_facto
                 for (int b = 0; b < T8; b++)
                     if (b < TX) Wt[a][b] += bb[a] * xx[b];
         }
-        __syncthreads(); /* everybody is done with [B A]': the buffer becomes W */
+        __syncthreads(); /* everybody is done with [B A]': the buffer becomes W (RIC0: [B A]' stays, W goes beside it) */
         GQP_TICK(1);
+        double *const Wd = RIC0 ? Wc : L.Bw;
 #pragma unroll
         for (int a = 0; a < T8; a++)
 #pragma unroll
             for (int b = 0; b < T8; b++)
             {
                 const int r = lr + 8 * a, c = lc + 8 * b;
-                if (b < TX && r < n && c < NX) L.Bw[r * SX + c] = Wt[a][b];
+                if (b < TX && r < n && c < NX) Wd[r * SX + c] = Wt[a][b];
             }
         /* ---- tiles of H (only now: the W tiles are dead, the two never share registers) ---- */
         double Mt[T8][T8];
@@ -1106,21 +1122,29 @@ __global__ void __launch_bounds__(64) GQP_WAVES_PER_EU(T8 <= 4 ? 2 : 1) kw_facto
                 Mt[a][b] = (r < n && c <= r) ? L.Hp[PK(r, c)] : (r == c ? 1.0 : 0.0);
             }
         __syncthreads();
-        /* w0 = Lx+' rb + lx+ */
+        /* w0 = Lx+' rb + lx+ ; RIC0: w0 = P+ rb + p+ (then [B A]' w0 is what W w0 is in the square-root form) */
         if (lane < NX)
         {
             double a = L.lx[lane];
-            GQP_DOT_UNROLL
-            for (int q = lane; q < NX; q++) a += L.Lx[q * SX + lane] * L.rb[q];
+            if (RIC0)
+            {
+                GQP_DOT_UNROLL
+                for (int q = 0; q < NX; q++) a += L.Lx[lane * SX + q] * L.rb[q];
+            }
+            else
+            {
+                GQP_DOT_UNROLL
+                for (int q = lane; q < NX; q++) a += L.Lx[q * SX + lane] * L.rb[q];
+            }
             L.w0[lane] = a;
         }
-        /* ---- M = H + reg + Gamma + W W' in tiles ---- */
+        /* ---- M = H + reg + Gamma + W W' in tiles; RIC0: M = H + reg + Gamma + W [B A] ---- */
 #pragma unroll (T8 == 4 && !GEN ? 4 : 2)
         for (int q = 0; q < NX; q++)
         {
             double wr[T8], wc[T8];
 #pragma unroll
-            for (int a = 0; a < T8; a++) wr[a] = L.Bw[(lr + 8 * a) * SX + q];
+            for (int a = 0; a < T8; a++) wr[a] = Wd[(lr + 8 * a) * SX + q];
 #pragma unroll
             for (int b = 0; b < T8; b++) wc[b] = L.Bw[(lc + 8 * b) * SX + q];
 #pragma unroll
@@ -1194,7 +1218,9 @@ __global__ void __launch_bounds__(64) GQP_WAVES_PER_EU(T8 <= 4 ? 2 : 1) kw_facto
             m = fixed ? 0.0 : gt + gadd + a;
         }
 
-        /* ---- Cholesky, column by column; rhs entry m of variable `lane` rides along ---- */
+        /* ---- Cholesky, column by column; rhs entry m of variable `lane` rides along.  RIC0, k >= 1: the input columns only,
+         * the trailing block and rhs entries are left as P_k and p_k ---- */
+        const int jend = (RIC0 && k > 0) ? NU : n;
         int pb = 0;
 #pragma unroll
         for (int jb = 0; jb < T8; jb++)
@@ -1202,7 +1228,7 @@ __global__ void __launch_bounds__(64) GQP_WAVES_PER_EU(T8 <= 4 ? 2 : 1) kw_facto
             for (int jj = 0; jj < 8; jj++)
             {
                 const int j = 8 * jb + jj;
-                if (j >= n) break;
+                if (j >= jend) break;
                 double *cb = L.cb + pb * 72;
                 pb ^= 1;
                 if (lc == jj)
@@ -1261,8 +1287,16 @@ __global__ void __launch_bounds__(64) GQP_WAVES_PER_EU(T8 <= 4 ? 2 : 1) kw_facto
             {
                 const int r = lr + 8 * a, c = lc + 8 * b;
                 if (b <= a && r < n && c <= r) L.Hp[PK(r, c)] = Mt[a][b];
-                /* x-block for the next (earlier) stage, explicit zeros above the diagonal */
-                if (r >= NU && r < n && c >= NU && c < n) L.Lx[(r - NU) * SX + c - NU] = (b <= a && c <= r) ? Mt[a][b] : 0.0;
+                /* x-block for the next (earlier) stage, explicit zeros above the diagonal; RIC0: P_k in full (both triangles) */
+                if (RIC0)
+                {
+                    if (b <= a && r < n && c >= NU && c <= r)
+                    {
+                        L.Lx[(r - NU) * SX + c - NU] = Mt[a][b];
+                        L.Lx[(c - NU) * SX + r - NU] = Mt[a][b];
+                    }
+                }
+                else if (r >= NU && r < n && c >= NU && c < n) L.Lx[(r - NU) * SX + c - NU] = (b <= a && c <= r) ? Mt[a][b] : 0.0;
             }
         if (mine)
         {
@@ -1381,7 +1415,8 @@ __device__ static inline void wpi_load_B(double *__restrict__ dst, int SXb, cons
     }
 }
 
-template <bool GEN, int CNX = 0, int CNU = 0>
+/* RIC0: the classical layout of kw_factor<..., RIC0> (x-block of Lf = P, lf = [lu; p] behind stage 0) */
+template <bool GEN, int CNX = 0, int CNU = 0, bool RIC0 = false>
 __global__ void __launch_bounds__(64) kw_backrhs(GqpDev D, GqpOpts O, int redo)
 {
     GQP_DYN_SHARED(smem);
@@ -1509,20 +1544,33 @@ __global__ void __launch_bounds__(64) kw_backrhs(GqpDev D, GqpOpts O, int redo)
         }
         __syncthreads();
         const double pf = k > 0 ? wpi_touch(D.Lf, NP, D.BAt, n * NX, inst, k - 1, lane) : 0.0;
-        /* y = Lx+ (Lx+' rb) + p+ with the x-block of the factor handled one stage ago */
-        if (lane < NX)
+        /* y = Lx+ (Lx+' rb) + p+ with the x-block of the factor handled one stage ago; RIC0: y = P+ rb + p+ */
+        if (!RIC0)
         {
-            double a = 0.0;
-            GQP_DOT_UNROLL
-            for (int q = lane; q < NX; q++) a += Ln[PK(NU + q, NU + lane)] * L.rb[q];
-            L.w0[lane] = a;
+            if (lane < NX)
+            {
+                double a = 0.0;
+                GQP_DOT_UNROLL
+                for (int q = lane; q < NX; q++) a += Ln[PK(NU + q, NU + lane)] * L.rb[q];
+                L.w0[lane] = a;
+            }
+            __syncthreads();
         }
-        __syncthreads();
         if (lane < NX)
         {
             double a = L.pn[lane];
-            GQP_DOT_UNROLL
-            for (int c = 0; c <= lane; c++) a += Ln[PK(NU + lane, NU + c)] * L.w0[c];
+            if (RIC0)
+            {
+                GQP_DOT_UNROLL
+                for (int c = 0; c < lane; c++) a += Ln[PK(NU + lane, NU + c)] * L.rb[c];
+                GQP_DOT_UNROLL
+                for (int q = lane; q < NX; q++) a += Ln[PK(NU + q, NU + lane)] * L.rb[q];
+            }
+            else
+            {
+                GQP_DOT_UNROLL
+                for (int c = 0; c <= lane; c++) a += Ln[PK(NU + lane, NU + c)] * L.w0[c];
+            }
             L.y[lane] = a;
         }
         __syncthreads();
@@ -1557,8 +1605,9 @@ __global__ void __launch_bounds__(64) kw_backrhs(GqpDev D, GqpOpts O, int redo)
     }
 }
 
-/* forward sweep; PFORM (= CORR): lf holds [l_u; p], otherwise the plain l of the factor sweep */
-template <bool CORR, bool GEN, int CNX = 0, int CNU = 0>
+/* forward sweep; PFORM (= CORR): lf holds [l_u; p], otherwise the plain l of the factor sweep.
+ * RIC0: the classical layout of kw_factor<..., RIC0>: dpi_k = P_k dx + p_k behind stage 0 */
+template <bool CORR, bool GEN, int CNX = 0, int CNU = 0, bool RIC0 = false>
 __global__ void __launch_bounds__(64) kw_fwd(GqpDev D, GqpOpts O, int redo)
 {
     GQP_DYN_SHARED(smem);
@@ -1645,23 +1694,38 @@ __global__ void __launch_bounds__(64) kw_fwd(GqpDev D, GqpOpts O, int redo)
                 lv -= lrj * L.bc[j & 1];
             }
         }
-        /* dpi_k = Lx (Lx' dx + l_x)  resp.  Lx (Lx' dx) + p */
+        /* dpi_k = Lx (Lx' dx + l_x)  resp.  Lx (Lx' dx) + p ; RIC0: P dx + p */
         if (CORR && k > 0)
         {
-            if (lane < NX)
+            if (RIC0)
             {
-                double a = 0.0;
-                GQP_DOT_UNROLL
-                for (int q = lane; q < NX; q++) a += Lc[PK(NU + q, NU + lane)] * L.dx[q];
-                L.w0[lane] = a;
+                if (lane < NX)
+                {
+                    double a = 0.0;
+                    GQP_DOT_UNROLL
+                    for (int c = 0; c < lane; c++) a += Lc[PK(NU + lane, NU + c)] * L.dx[c];
+                    GQP_DOT_UNROLL
+                    for (int q = lane; q < NX; q++) a += Lc[PK(NU + q, NU + lane)] * L.dx[q];
+                    L.y[lane] = a;
+                }
             }
-            __syncthreads();
-            if (lane < NX)
+            else
             {
-                double a = 0.0;
-                GQP_DOT_UNROLL
-                for (int c = 0; c <= lane; c++) a += Lc[PK(NU + lane, NU + c)] * L.w0[c];
-                L.y[lane] = a; /* + p of this lane's state, added by its owner below */
+                if (lane < NX)
+                {
+                    double a = 0.0;
+                    GQP_DOT_UNROLL
+                    for (int q = lane; q < NX; q++) a += Lc[PK(NU + q, NU + lane)] * L.dx[q];
+                    L.w0[lane] = a;
+                }
+                __syncthreads();
+                if (lane < NX)
+                {
+                    double a = 0.0;
+                    GQP_DOT_UNROLL
+                    for (int c = 0; c <= lane; c++) a += Lc[PK(NU + lane, NU + c)] * L.w0[c];
+                    L.y[lane] = a; /* + p of this lane's state, added by its owner below */
+                }
             }
             __syncthreads();
             if (mine && lane >= NU) WAT(D.dpi, k * NX + lane - NU) = L.y[lane - NU] + lv;

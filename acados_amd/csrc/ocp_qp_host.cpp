@@ -862,13 +862,13 @@ void ocp_qp_gpu_ipm_opts_set(void *config, void *opts_, const char *field, void 
     }
     else if (!strcmp(field, "ric_alg"))
     {
-        /* ric_alg 0 (classical Riccati: P carried unfactored, only R + B'PB must be positive definite --
-         * acados_ocp_options.py:1084-1101) exists for full-space Hessians that are indefinite; every kernel family here
-         * carries the Cholesky factor of P (square-root form, ric_alg 1, the acados default).  Accepting 0 and running the
-         * square-root form would factorise an indefinite block silently: refused like a wrong field. */
-        if (*i != 1)
+        /* acados_ocp_options.py:1084-1101: 1 square-root Riccati (the acados default; the full-space stage Hessian must be
+         * positive definite), 0 classical (P carried unfactored: only R + B'PB must be, the stage blocks may be indefinite).
+         * Passed to the device batch with the other options; 0 runs the classical sweeps of the wave-per-instance family
+         * whatever family the shape would otherwise use. */
+        if (*i != 0 && *i != 1)
         {
-            printf("\nerror: ocp_qp_gpu_ipm_opts_set: ric_alg = %d not available in this backend (only the square-root Riccati recursion, ric_alg = 1)\n", *i);
+            printf("\nerror: ocp_qp_gpu_ipm_opts_set: ric_alg must be 0 or 1, got %d\n", *i);
             exit(1);
         }
         o->ric_alg = *i;
@@ -1128,6 +1128,7 @@ int gqp_host::gpu_ipm_evaluate_impl(void *config, int n, void **qp_in_, void **q
     ocp_qp_gpu_batch_opts_set(b, "lam0_min", &o->lam0_min);
     ocp_qp_gpu_batch_opts_set(b, "cond_pred_corr", &o->cond_pred_corr);
     ocp_qp_gpu_batch_opts_set(b, "print_level", &o->print_level);
+    ocp_qp_gpu_batch_opts_set(b, "ric_alg", &o->ric_alg);
     {
         /* the condensing request arrives as an argument (from the xcond level's opts); the device batch is told only
          * when it changes -- a change drops the resident condensed batch */
@@ -1300,6 +1301,10 @@ void ocp_qp_gpu_ipm_solver_get(void *config, void *qp_in_, void *qp_out, void *o
     ocp_qp_gpu_batch_get(m->cache->batch, "ric_L", stage, Lb.data(), 0);
     ocp_qp_gpu_batch_get(m->cache->batch, "ric_l", stage, lb.data(), 0);
     const double *L = Lb.data(), *l = lb.data(); /* instance 0: the QP this memory belongs to */
+    /* classical layout (ric_alg 0) behind stage 0: the x-block of L is the lower triangle of P itself, l = [lu; p] */
+    int ric_alg = 1;
+    ocp_qp_gpu_batch_get_int(m->cache->batch, "ric_alg", 0, &ric_alg);
+    const bool plain_P = ric_alg == 0 && stage > 0;
     auto bad_size = [&](int e1, int e2) {
         if (size1 != e1 || size2 != e2)
             printf("\nocp_qp_gpu_ipm_solver_get: size of field %s not as expected, got size %d %d.\n", field, size1, size2);
@@ -1310,6 +1315,11 @@ void ocp_qp_gpu_ipm_solver_get(void *config, void *qp_in_, void *qp_out, void *o
         for (int c = 0; c < nx; c++)
             for (int r = 0; r < nx; r++)
             {
+                if (plain_P)
+                {
+                    out[r + nx * c] = r >= c ? L[(nu + r) + nv * (nu + c)] : L[(nu + c) + nv * (nu + r)];
+                    continue;
+                }
                 double a = 0.0;
                 for (int q = 0; q <= (r < c ? r : c); q++) a += L[(nu + r) + nv * (nu + q)] * L[(nu + c) + nv * (nu + q)];
                 out[r + nx * c] = a;
@@ -1321,6 +1331,7 @@ void ocp_qp_gpu_ipm_solver_get(void *config, void *qp_in_, void *qp_out, void *o
         for (int r = 0; r < nx; r++)
         {
             double a = 0.0;
+            if (plain_P) { out[r] = l[nu + r]; continue; }
             for (int q = 0; q <= r; q++) a += L[(nu + r) + nv * (nu + q)] * l[nu + q];
             out[r] = a;
         }

@@ -204,7 +204,10 @@ void ocp_qp_gpu_pcond_opts_set(void *opts_, const char *field, void *value)
         opts->N2 = *(int *) value;
     }
     else if (!strcmp(field, "N_bkp")) opts->N2_bkp = *(int *) value;
-    else if (!strcmp(field, "ric_alg")) opts->ric_alg = *(int *) value; /* one condensing algorithm on the device */
+    /* cond_ric_alg selects HPIPM's condensing algorithm in the reference.  Condensing here is the direct contraction sum Z'HZ
+     * (pcond_kernels.hpp) with no Riccati step, so there is nothing for it to select; it is accepted and kept.  The Riccati
+     * recursion of the condensed QP is the inner solver's ric_alg, which the device batch hands to its condensed child. */
+    else if (!strcmp(field, "ric_alg")) opts->ric_alg = *(int *) value;
     else if (!strcmp(field, "block_size"))
     {
         for (int i = 0; i < opts->N2 + 1; i++) opts->block_size[i] = ((int *) value)[i];

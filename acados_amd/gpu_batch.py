@@ -202,8 +202,13 @@ class OcpQpGpuBatch:
         L = self.get("ric_L", stage).reshape(self.n_batch, nv, nv).transpose(0, 2, 1)  # column-major blocks
         l = self.get("ric_l", stage)
         Lr, Ls, Lx = L[:, :nu, :nu], L[:, nu:, :nu], L[:, nu:, nu:]
-        P = Lx @ Lx.transpose(0, 2, 1)
-        p = np.einsum("bij,bj->bi", Lx, l[:, nu:])
+        if self.ric_alg == 0 and stage > 0:
+            # classical layout: the x-block is the lower triangle of P itself, l = [lu; p] (stage 0 is the full factor)
+            P = np.tril(Lx) + np.tril(Lx, -1).transpose(0, 2, 1)
+            p = l[:, nu:].copy()
+        else:
+            P = Lx @ Lx.transpose(0, 2, 1)
+            p = np.einsum("bij,bj->bi", Lx, l[:, nu:])
         if nu:
             LrT = Lr.transpose(0, 2, 1)
             K = -np.linalg.solve(LrT, Ls.transpose(0, 2, 1))
@@ -261,6 +266,13 @@ class OcpQpGpuBatch:
     @property
     def stream(self):
         return self._L.ocp_qp_gpu_batch_stream(self._h)
+
+    @property
+    def ric_alg(self):
+        """Riccati recursion of the batch (option "ric_alg"): 1 square-root, 0 classical"""
+        out = np.zeros(1, dtype=np.int32)
+        self._L.ocp_qp_gpu_batch_get_int(self._h, b"ric_alg", 0, out.ctypes.data_as(C.POINTER(C.c_int)))
+        return int(out[0])
 
     @property
     def kernel_name(self):

@@ -218,9 +218,9 @@ static void gpu_opts_set(void *config, void *opts_, const char *field, void *val
     else if (!strcmp(field, "t0_init")) o->t0_init = *i;
     else if (!strcmp(field, "ric_alg"))
     {
-        /* the device kernels carry the Cholesky factor of P (square-root Riccati); the classical recursion for an indefinite
-         * full-space Hessian is not available: refused, not silently replaced */
-        if (*i != 1) { printf("\nerror: ocp_qp_gpu_ipm_opts_set: ric_alg = %d not available (only ric_alg = 1)\n", *i); exit(1); }
+        /* 1 square-root Riccati, 0 classical (indefinite stage blocks, positive definite reduced Hessian): the device batch
+         * runs the classical sweeps of its wave-per-instance family for 0 */
+        if (*i != 0 && *i != 1) { printf("\nerror: ocp_qp_gpu_ipm_opts_set: ric_alg must be 0 or 1, got %d\n", *i); exit(1); }
         o->ric_alg = *i;
     }
     else if (!strcmp(field, "tol_comp_soft_scale")) o->tol_comp_soft_scale = *d;
@@ -411,6 +411,7 @@ static void apply_opts(ocp_qp_gpu_batch *b, const ocp_qp_gpu_ipm_opts *o, int ws
     ocp_qp_gpu_batch_opts_set(b, "tau_min", &o->tau_min);
     ocp_qp_gpu_batch_opts_set(b, "tol_comp_soft_scale", &o->tol_comp_soft_scale);
     ocp_qp_gpu_batch_opts_set(b, "cond_pred_corr", &o->cond_pred_corr);
+    ocp_qp_gpu_batch_opts_set(b, "ric_alg", &o->ric_alg);
     /* partial condensing inside the device solve (0 = off; the library keeps its condensed batch while cond_N is unchanged) */
     ocp_qp_gpu_batch_opts_set(b, "cond_N", &o->cond_N);
     if (o->cond_N > 0 && o->cond_block_size_set) ocp_qp_gpu_batch_opts_set(b, "cond_block_size", o->cond_block_size);
