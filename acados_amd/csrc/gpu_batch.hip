@@ -28,6 +28,7 @@
 #include "pcond_kernels_w16.hpp"
 #include "pcond_kernels_mfma.hpp"
 #include "dense_kernels.hpp"
+#include "grad_kernels.hpp"
 #include "kernel_sets.h"
 
 /* a failing HIP call is not something a solve can recover from (lost device, out of HBM): message + exit(1), acados'
@@ -271,6 +272,19 @@ struct ocp_qp_gpu_batch
                                                         valid) are read from the mirrored element */
         gqp::GArrTable T;
     } bulk_in, bulk_out, bulk_seed, bulk_vec;
+    /* reverse-mode data gradients (grad_kernels.hpp): op table over the input blob, gather / gate table of the output blob,
+     * cotangent scatter table, the cotangent itself in the ux layout (the fixed variables' own term) */
+    struct GradMap
+    {
+        bool built = false;
+        int len = 0, olen = 0;
+        size_t lds = 0;
+        gqp::GradOp *d_ops = nullptr;
+        gqp::GradTerm *d_terms = nullptr;
+        int *d_oarr = nullptr, *d_oelem = nullptr, *d_ogate = nullptr, *d_ckind = nullptr, *d_celem = nullptr, *d_bad = nullptr;
+        GArr cot = {nullptr, 0, 0};
+        bool seeded = false; /* an adjoint seed is in the residual arrays: data_grad may run */
+    } grad;
 };
 
 namespace
@@ -3214,6 +3228,202 @@ try
     const dim3 grid((b->B + 63) / 64, (len + 255) / 256), block(64);
     bulk_gather_launch(b, dst, len, M.d_arr, M.d_elem, T);
     if (!is_device) HIPCHK(hipMemcpyAsync(blob, dst, sizeof(double) * cnt, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+}
+catch (const gqp_hip_failure &) { return -1; }
+
+/* ---- reverse-mode data gradients (grad_kernels.hpp, DESIGN.md "Data gradients") ---- */
+static void grad_build(ocp_qp_gpu_batch *b)
+{
+    auto &G = b->grad;
+    if (G.built) return;
+    const int len = gqp_bulk_len_impl(b, 0), olen = gqp_bulk_len_impl(b, 1);
+    const auto &Mi = b->bulk_in, &Mo = b->bulk_out;
+    const int N = b->N, NX = b->ks->NX, NU = b->ks->NU, n = NX + NU, NP = n * (n + 1) / 2;
+    auto ob = [&](const char *f, int k) { int l = 0; const int o = gqp_bulk_offset_impl(b, 1, f, k, &l); return l > 0 ? o : -1; };
+    /* output blob: gather map renumbered to the kernel's tables, activity gates, cotangent destinations */
+    std::vector<int> oarr(olen, -1), oelem(olen, 0), ogate(olen, -1), ckind(olen, 0), celem(olen, 0);
+    {
+        std::vector<int> ha(olen), he(olen);
+        HIPCHK(hipMemcpy(ha.data(), Mo.d_arr, sizeof(int) * olen, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(he.data(), Mo.d_elem, sizeof(int) * olen, hipMemcpyDeviceToHost));
+        for (int e = 0; e < olen; e++) { oarr[e] = ha[e] >= 7 && ha[e] <= 11 ? ha[e] - 7 : -1; oelem[e] = he[e]; }
+    }
+    for (size_t q = 0; q < Mo.fields.size(); q++)
+    {
+        const std::string &f = Mo.fields[q];
+        const int k = Mo.seg_stage[q], o = Mo.seg_off[q], l = Mo.seg_len[q];
+        const GqpStage &S = b->st[k];
+        const int nbg = S.nb + S.ng;
+        for (int e = 0; e < l; e++)
+        {
+            if (f == "u" || f == "x")
+            {
+                const int pv = oelem[o + e] - k * n;
+                ckind[o + e] = ((S.emask >> pv) & 1) ? 3 : 1;
+                celem[o + e] = oelem[o + e];
+            }
+            else if (f == "sl" || f == "su") { ckind[o + e] = 2; celem[o + e] = oelem[o + e]; }
+            if (f == "lam" || f == "t")
+            {
+                const int bit = oelem[o + e] - S.o_ct;
+                ogate[o + e] = (k * b->AW + bit / 64) * 64 + bit % 64;
+                if (e < 2 * nbg)
+                {
+                    const int r = e % nbg; /* original row order: box rows, then general rows */
+                    if (r < S.nb && std::find(b->idxe[k].begin(), b->idxe[k].end(), r) != b->idxe[k].end()) ogate[o + e] = -2;
+                }
+            }
+        }
+    }
+    /* input blob: one op per entry */
+    std::vector<gqp::GradOp> ops(len, gqp::GradOp{0, 0, -1, 0, 0.0});
+    std::vector<gqp::GradTerm> terms;
+    for (size_t q = 0; q < Mi.fields.size(); q++)
+    {
+        const std::string &f = Mi.fields[q];
+        const int k = Mi.seg_stage[q], o = Mi.seg_off[q], l = Mi.seg_len[q];
+        const GqpStage &S = b->st[k];
+        const int nx = b->nx[k], nu = b->nu[k], nx1 = k < N ? b->nx[k + 1] : 0, ng = S.ng, nb = S.nb, nbg = nb + ng, ns = S.ns;
+        const int ou = ob("u", k), ox = ob("x", k), osl = ob("sl", k), osu = ob("su", k), opi = k < N ? ob("pi", k) : -1, olam = ob("lam", k);
+        auto vec = [&](int e, int a, double c) { ops[o + e] = gqp::GradOp{1, a, -1, 0, c}; };
+        auto prod = [&](int e, int a, int a2, int bb, double c) { ops[o + e] = gqp::GradOp{2, a, a2, bb, c}; };
+        auto is_eq = [&](int row) { return std::find(b->idxe[k].begin(), b->idxe[k].end(), row) != b->idxe[k].end(); };
+        const bool bnd = f == "lbu" || f == "ubu" || f == "lbx" || f == "ubx";
+        for (int e = 0; e < l; e++)
+        {
+            if (f == "A") prod(e, opi + e % nx1, -1, ox + e / nx1, 1.0);
+            else if (f == "B") prod(e, opi + e % nx1, -1, ou + e / nx1, 1.0);
+            else if (f == "b") vec(e, opi + e, 1.0);
+            else if (f == "Q") prod(e, ox + e % nx, -1, ox + e / nx, 0.5);
+            else if (f == "R") prod(e, ou + e % nu, -1, ou + e / nu, 0.5);
+            else if (f == "S") prod(e, ou + e % nu, -1, ox + e / nu, 1.0);
+            else if (f == "q") vec(e, ox + e, 1.0);
+            else if (f == "r") vec(e, ou + e, 1.0);
+            else if (bnd)
+            {
+                const int row = (f[2] == 'x' ? b->nbu[k] : 0) + e;
+                if (!is_eq(row)) vec(e, olam + (f[0] == 'u' ? nbg : 0) + row, f[0] == 'u' ? -1.0 : 1.0);
+            }
+            else if (f == "lg") vec(e, olam + nb + e, 1.0);
+            else if (f == "ug") vec(e, olam + nbg + nb + e, -1.0);
+            else if (f == "C") prod(e, olam + nbg + nb + e % ng, olam + nb + e % ng, ox + e / ng, 1.0);
+            else if (f == "D") prod(e, olam + nbg + nb + e % ng, olam + nb + e % ng, ou + e / ng, 1.0);
+            else if (f == "Zl") prod(e, osl + e, -1, osl + e, 0.5);
+            else if (f == "Zu") prod(e, osu + e, -1, osu + e, 0.5);
+            else if (f == "zl") vec(e, osl + e, 1.0);
+            else if (f == "zu") vec(e, osu + e, 1.0);
+            else if (f == "lls") vec(e, olam + 2 * nbg + e, 1.0);
+            else if (f == "lus") vec(e, olam + 2 * nbg + ns + e, 1.0);
+            else if (f == "lbx#value")
+            {
+                const int row = b->nbu[k] + e;
+                if (!is_eq(row)) continue;
+                /* the value of a fixed variable: its stationarity row applied to the adjoint direction, plus its own cotangent */
+                const int vi = b->idxb[k][row], j = padded_var(b, k, vi);
+                const int t0 = (int) terms.size();
+                terms.push_back(gqp::GradTerm{13, k * n + j, -1, 0, 1.0});
+                for (int r = 0; r < nu + nx; r++)
+                {
+                    const int pr = padded_var(b, k, r);
+                    terms.push_back(gqp::GradTerm{10, k * NP + (pr >= j ? PK(pr, j) : PK(j, pr)), r < nu ? ou + r : ox + r - nu, 0, 1.0});
+                }
+                for (int c = 0; c < nx1; c++) terms.push_back(gqp::GradTerm{11, (k * n + j) * NX + c, opi + c, 0, 1.0});
+                if (vi >= nu && k > 0) terms.push_back(gqp::GradTerm{-1, 0, ob("pi", k - 1) + vi - nu, 0, -1.0});
+                for (int g = 0; g < ng; g++)
+                {
+                    terms.push_back(gqp::GradTerm{12, (S.o_g + g) * n + j, olam + nbg + nb + g, 0, 1.0});
+                    terms.push_back(gqp::GradTerm{12, (S.o_g + g) * n + j, olam + nb + g, 0, -1.0});
+                }
+                ops[o + e] = gqp::GradOp{3, t0, (int) terms.size(), 0, 0.0};
+            }
+        }
+    }
+    G.len = len;
+    G.olen = olen;
+    G.lds = sizeof(double) * 2 * (size_t) olen;
+    G.d_ops = dalloc<gqp::GradOp>(b, len);
+    G.d_terms = dalloc<gqp::GradTerm>(b, terms.size());
+    G.d_oarr = dalloc<int>(b, olen); G.d_oelem = dalloc<int>(b, olen); G.d_ogate = dalloc<int>(b, olen);
+    G.d_ckind = dalloc<int>(b, olen); G.d_celem = dalloc<int>(b, olen);
+    G.d_bad = dalloc<int>(b, 1);
+    if (len) HIPCHK(hipMemcpy(G.d_ops, ops.data(), sizeof(gqp::GradOp) * len, hipMemcpyHostToDevice));
+    if (!terms.empty()) HIPCHK(hipMemcpy(G.d_terms, terms.data(), sizeof(gqp::GradTerm) * terms.size(), hipMemcpyHostToDevice));
+    const std::pair<int *, std::vector<int> *> up[] = {{G.d_oarr, &oarr}, {G.d_oelem, &oelem}, {G.d_ogate, &ogate}, {G.d_ckind, &ckind}, {G.d_celem, &celem}};
+    for (auto &u : up)
+        if (olen) HIPCHK(hipMemcpy(u.first, u.second->data(), sizeof(int) * olen, hipMemcpyHostToDevice));
+    G.cot = garr<double>(b, (size_t) (N + 2) * n);
+    if (G.lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *) gqp::k_data_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int) G.lds));
+    G.built = true;
+}
+
+int ocp_qp_gpu_batch_adj_seed_bulk(ocp_qp_gpu_batch *b, const double *cot, int is_device)
+try
+{
+    HIPCHK(hipSetDevice(b->device));
+    grad_build(b);
+    auto &G = b->grad;
+    if (G.lds > 160 * 1024)
+    {
+        fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_adj_seed_bulk: the solution of one instance (%d doubles) does not fit the LDS of a workgroup\n", G.olen);
+        return -1;
+    }
+    G.seeded = false;
+    if (sens_begin(b)) return -1; /* zeroes the seed arrays, factorises at the solution where the sweeps run in place */
+    const double *src = stage_in(b, cot, (size_t) b->B * G.olen, is_device);
+    HIPCHK(hipMemsetAsync(G.d_bad, 0, sizeof(int), b->stream));
+    HIPCHK(hipMemsetAsync(G.cot.p, 0, sizeof(double) * (size_t) G.cot.E * b->Bp, b->stream));
+    if (G.olen)
+        hipLaunchKernelGGL(gqp::k_adj_seed, dim3((G.olen + 255) / 256, b->B), dim3(256), 0, b->stream, src, b->B, G.olen, G.d_ckind, G.d_celem,
+                           b->D.rg, b->D.rgs, G.cot, G.d_bad);
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, G.d_bad, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    if (bad)
+    {
+        fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_adj_seed_bulk: cotangents on pi / lam / t are not supported (only u x sl su)\n");
+        sens_begin(b); /* leave an all-zero seed set, not a partial one */
+        HIPCHK(hipMemsetAsync(b->D.rg.p, 0, sizeof(double) * (size_t) b->D.rg.E * b->Bp, b->stream));
+        HIPCHK(hipMemsetAsync(b->D.rgs.p, 0, sizeof(double) * (size_t) b->D.rgs.E * b->Bp, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return -1;
+    }
+    G.seeded = true;
+    return 0;
+}
+catch (const gqp_hip_failure &) { return -1; }
+
+int ocp_qp_gpu_batch_data_grad_bulk(ocp_qp_gpu_batch *b, double *grad, int is_device)
+try
+{
+    HIPCHK(hipSetDevice(b->device));
+    grad_build(b);
+    auto &G = b->grad;
+    if (!G.seeded || !b->sens_open)
+    {
+        fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_data_grad_bulk: no adjoint seed (call ocp_qp_gpu_batch_adj_seed_bulk after the solve)\n");
+        return -1;
+    }
+    G.seeded = false;
+    if (ocp_qp_gpu_batch_sens_solve(b)) return -1; /* the adjoint direction, in dux dsv dpi dlam dt */
+    const size_t cnt = (size_t) b->B * G.len;
+    double *dst = grad;
+    if (!is_device)
+    {
+        if (cnt > b->stage_cap) { b->stage_cap = cnt * 2; b->d_stage = dalloc<double>(b, b->stage_cap); }
+        dst = b->d_stage;
+    }
+    const GqpDev &D = b->D;
+    gqp::GArrTable T;
+    const GArr tab[14] = {D.ux, D.sv, D.pi, D.lam, D.t, D.dux, D.dsv, D.dpi, D.dlam, D.dt, D.RSQ, D.BAt, D.DCt, G.cot};
+    for (int q = 0; q < 16; q++) T.a[q] = q < 14 ? tab[q] : GArr{nullptr, 0, 0};
+    const int per = (b->B + GQP_GRAD_XCD - 1) / GQP_GRAD_XCD;
+    if (G.len)
+        GQP_LAUNCH_COOP(gqp::k_data_grad, dim3(per * GQP_GRAD_XCD), dim3(GQP_GRAD_THREADS), G.lds, b->stream, dst, b->B, G.len, G.d_ops, G.d_terms,
+                        G.olen, G.d_oarr, G.d_oelem, G.d_ogate, T, D.amask, D.status, per);
+    HIPCHK(hipGetLastError());
+    if (!is_device) HIPCHK(hipMemcpyAsync(grad, dst, sizeof(double) * cnt, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
 }

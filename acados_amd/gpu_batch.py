@@ -232,6 +232,59 @@ class OcpQpGpuBatch:
         if self._L.ocp_qp_gpu_batch_sens_solve(self._h) != 0:
             raise RuntimeError("ocp_qp_gpu_batch_sens_solve failed")
 
+    # -- bulk blobs (ocp_qp_gpu_batch_bulk_len / _offset: output 0 = QP data, 1 = solution u x sl su pi lam t) --------------
+    def bulk_len(self, output):
+        n = self._L.ocp_qp_gpu_batch_bulk_len(self._h, int(output))
+        if n < 0:
+            raise RuntimeError("ocp_qp_gpu_batch_bulk_len failed")
+        return n
+
+    def bulk_offset(self, output, field, stage):
+        """(offset, length) of one field of one stage in the per-instance blob; (-1, 0) where the stage has no such field"""
+        n = C.c_int(0)
+        off = self._L.ocp_qp_gpu_batch_bulk_offset(self._h, int(output), field.encode(), int(stage), C.byref(n))
+        return int(off), int(n.value)
+
+    def _blob_call(self, fn, blob, output, what):
+        """blob: NumPy [n_batch, len] (host copy) or a contiguous float64 CUDA tensor of the same shape (device pointer)"""
+        shape = (self.n_batch, self.bulk_len(output))
+        if hasattr(blob, "data_ptr") and getattr(blob, "is_cuda", False):
+            assert blob.is_contiguous() and str(blob.dtype) == "torch.float64" and tuple(blob.shape) == shape, (blob.shape, shape)
+            rc = fn(self._h, C.c_void_p(blob.data_ptr()), 1)
+        else:
+            assert blob.flags.c_contiguous and blob.dtype == np.float64 and blob.shape == shape, (blob.shape, shape)
+            rc = fn(self._h, blob.ctypes.data_as(C.c_void_p), 0)
+        if rc != 0:
+            raise RuntimeError(f"{what} failed")
+        return blob
+
+    def set_bulk(self, blob):
+        """every numeric field of every stage in one go (input blob layout)"""
+        self._blob_call(self._L.ocp_qp_gpu_batch_set_bulk, blob, 0, "ocp_qp_gpu_batch_set_bulk")
+
+    def get_bulk_in(self, out=None):
+        """the QP data in the input blob layout; `out` may be a CUDA tensor (written in place on the device)"""
+        out = np.zeros((self.n_batch, self.bulk_len(0))) if out is None else out
+        return self._blob_call(self._L.ocp_qp_gpu_batch_get_bulk_in, out, 0, "ocp_qp_gpu_batch_get_bulk_in")
+
+    def get_bulk(self, out=None):
+        """the solution in the output blob layout; `out` may be a CUDA tensor"""
+        out = np.zeros((self.n_batch, self.bulk_len(1))) if out is None else out
+        return self._blob_call(self._L.ocp_qp_gpu_batch_get_bulk, out, 1, "ocp_qp_gpu_batch_get_bulk")
+
+    def data_grad(self, cot):
+        """reverse-mode gradient of L(solution) w.r.t. the QP data (ocp_qp_gpu_batch_adj_seed_bulk + _data_grad_bulk).  cot:
+        dL/d(solution) in the output blob layout [n_batch, bulk_len(1)] (u x sl su used; pi lam t must be zero), NumPy or a
+        CUDA float64 tensor; returns dL/d(data) in the input blob layout [n_batch, bulk_len(0)], of the same kind.  Q and R carry
+        the symmetric gradient in both triangles; instances whose last solve failed get a zero row."""
+        self._blob_call(self._L.ocp_qp_gpu_batch_adj_seed_bulk, cot, 1, "ocp_qp_gpu_batch_adj_seed_bulk")
+        if hasattr(cot, "data_ptr") and getattr(cot, "is_cuda", False):
+            import torch
+            grad = torch.empty((self.n_batch, self.bulk_len(0)), dtype=torch.float64, device=cot.device)
+        else:
+            grad = np.zeros((self.n_batch, self.bulk_len(0)))
+        return self._blob_call(self._L.ocp_qp_gpu_batch_data_grad_bulk, grad, 0, "ocp_qp_gpu_batch_data_grad_bulk")
+
     # -- KKT residuals of whatever (data, iterate) is in HBM (ocp_qp_res_compute / _nrm_inf) ----------------
     def res_compute(self):
         """residual vectors of the current iterate, one launch of a kernel independent of the IPM sweeps; read them with

@@ -173,6 +173,21 @@ int ocp_qp_gpu_batch_sens_bulk_offset(ocp_qp_gpu_batch *b, int output, const cha
 int ocp_qp_gpu_batch_sens_set_bulk(ocp_qp_gpu_batch *b, const double *blob, int is_device);
 int ocp_qp_gpu_batch_sens_get_bulk(ocp_qp_gpu_batch *b, double *blob, int is_device);
 
+/* Reverse-mode gradient of a loss L(u, x, sl, su) of the solution w.r.t. EVERY entry of the QP data ("Data gradients"):
+ * one adjoint solve with the KKT matrix at the final iterate (the sweeps of _sens_solve, seeded with the cotangent) and one
+ * contraction kernel over the input blob.  Call after a solve:
+ *   _adj_seed_bulk   `cot` = dL/d(solution) in the OUTPUT blob layout (_bulk_len / _bulk_offset with output = 1); the u x sl su
+ *                    entries are used, any nonzero pi / lam / t entry is refused (-1).  Opens a fresh seed set like _sens_set_bulk.
+ *   _data_grad_bulk  runs the adjoint sweeps and writes `grad` in the INPUT blob layout (output = 0): entry e is dL/d(blob[e]) as
+ *                    _set_bulk reads it -- vectors, bounds, slack weights, A B C D S entry by entry; masks and the bound entry of an
+ *                    equality-flagged row get 0, its value (the "lbx#value" segment, e.g. x0) the whole derivative.  Exception: Q
+ *                    and R hold the SYMMETRIC gradient G in both triangles, so that a symmetric perturbation dH changes L by
+ *                    sum_ij G_ij dH_ij (a single entry of the lower triangle moves L by G_ij, a pair (i,j), (j,i) by 2 G_ij).
+ * Instances whose last solve did not end with status 0 get an all-zero row.  `is_device` != 0: device pointers, no host copy.
+ * Works wherever _sens_solve does (every kernel family, ric_alg 0 / 1, after partial condensing, on the dense path). */
+int ocp_qp_gpu_batch_adj_seed_bulk(ocp_qp_gpu_batch *b, const double *cot, int is_device);
+int ocp_qp_gpu_batch_data_grad_bulk(ocp_qp_gpu_batch *b, double *grad, int is_device);
+
 /* KKT residuals of an arbitrary (qp_in, qp_out): what ocp_qp_res_compute -> d_ocp_qp_res_compute and
  * ocp_qp_res_compute_nrm_inf do (acados/ocp_qp/ocp_qp_common.c:559-667; wrapper ocp_qp_inf_norm_residuals,
  * interfaces/acados_c/ocp_qp_interface.c:642-650; asserted by test/ocp_qp/test_qpsolvers.cpp:240-251).  _res_compute
