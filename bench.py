@@ -6,10 +6,16 @@ every instance), inputs already packed and resident in HBM when the timed region
 Workload at N=1 GPU: BASELINE.json configs[1] (C2) -- random LQR-like OCP-QP, N=50, nx=8, nu=3,
 batch=65,536, u-box + x0 equality, tolerances 1e-8, iter_max 50 (SURVEY.md 8d "C2 input").
 N>1: one process per GPU (torch.distributed.run), the batch is sharded by instance -- every rank
-solves its own 65,536 instances (weak scaling), no data-path collective; AFTER the timed region the
-full solution payload {ux, pi, lam, t, status, iter, solve time} of every rank is gathered with ONE
-RCCL all-gather over xGMI from device buffers through the library's own collective entry
+solves its own 65,536 instances (weak scaling), no data-path collective; with --full, AFTER the timed
+region the full solution payload {ux, pi, lam, t, status, iter, solve time} of every rank is gathered
+with ONE RCCL all-gather over xGMI from device buffers through the library's own collective entry
 (ocp_qp_gpu_batch_gather; its time is reported as gather_ms).
+
+A plain run does what the headline figure needs: it sets up, warms up, times the steps, writes
+--dump-outputs and prints the line; its `ipm` statistics and `roofline` are read from the timed solves.
+--full adds, after that and outside the timed region, everything that takes work of its own: the oracle
+checks and the independently recomputed KKT residual of the headline batch, `configs`, `cpu_baseline`
+and the solutions gather.
 
 Extra objects on the JSON line:
   roofline     dominant kernel (by accumulated HIP-event time inside the timed region, events on the
@@ -21,12 +27,12 @@ Extra objects on the JSON line:
                gfx950 correction of MI355X_MICROARCH.md), read from the newest profiles/*_pmc_traffic.json
                whose recorded commit is reported next to it; `full_launch` repeats both for the launches in
                which every instance is still iterating.
-  configs      the other single-GPU configurations of BASELINE.json (C3, C4, the per-GPU share of C5),
-               each with solves/s, iterations, failures, independently recomputed KKT residual, oracle
-               error on a sample, dominant kernel and its roofline fraction (rank 0, N=1 only).
-  cpu_baseline the oracle (restated CPU port, NOT HPIPM: its sources are absent from the reference
-               tree) on a bounded sample of the same workload on the host cores, rank 0, N=1 only:
-               one-thread rate, best thread count of a sweep, cores visible / allowed.
+  configs      (--full) the other single-GPU configurations of BASELINE.json (C3, C4, the per-GPU share
+               of C5), each with solves/s, iterations, failures, independently recomputed KKT residual,
+               oracle error on a sample, dominant kernel and its roofline fraction (rank 0, N=1 only).
+  cpu_baseline (--full) the oracle (restated CPU port, NOT HPIPM: its sources are absent from the
+               reference tree) on a bounded sample of the same workload on the host cores, rank 0, N=1
+               only: one-thread rate, best thread count of a sweep, cores visible / allowed.
 """
 import argparse
 import glob
@@ -79,17 +85,21 @@ def main():
     ap.add_argument("--horizon", type=int, default=50)
     ap.add_argument("--nx", type=int, default=8)
     ap.add_argument("--nu", type=int, default=3)
-    ap.add_argument("--cpu-sample", type=int, default=2048, help="unique instances built for the CPU baseline / parity sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip C3 / C4 / C5 (the headline line only)")
-    ap.add_argument("--c4-batch", type=int, default=16384)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the oracle checks and the independent KKT "
+                         "residual of the headline batch, the CPU baseline, the other configurations and the solutions gather (the options "
+                         "marked (--full) shape these)")
+    ap.add_argument("--cpu-sample", type=int, default=2048, help="(--full) unique instances built for the CPU baseline / parity sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) skip C3 / C4 / C5 and the oracle check of --check-configs")
+    ap.add_argument("--c4-batch", type=int, default=16384, help="(--full) instances of C4")
     ap.add_argument("--check-configs", type=int, default=1024,
-                    help="instances per configuration checked against the oracle (OpenMP batch on the host, outside timing; SURVEY 8d asks >= 1,024)")
-    ap.add_argument("--boundary-n", type=int, default=4096, help="capsules of the through-the-boundary leg (configs.boundary_C3)")
+                    help="(--full) instances per configuration checked against the oracle (OpenMP batch on the host, outside timing; SURVEY 8d asks >= 1,024)")
+    ap.add_argument("--boundary-n", type=int, default=4096, help="(--full) capsules of the through-the-boundary leg (configs.boundary_C3)")
     ap.add_argument("--polish-legs", action="store_true",
-                    help="also time the opt-in terminal polishing step on C2 / C4 (measured and dominated by a tighter tol_comp: profiles/r06_polish_sweep.txt)")
+                    help="(--full) also time the opt-in terminal polishing step on C2 / C4 (measured and dominated by a tighter tol_comp: profiles/r06_polish_sweep.txt)")
     ap.add_argument("--compact-min", type=int, default=None, help="override the library default of the compaction threshold")
-    ap.add_argument("--check", type=int, default=8, help="instances per rank checked against the oracle (outside timing)")
+    ap.add_argument("--check", type=int, default=8, help="(--full) instances per rank checked against the oracle (outside timing)")
     ap.add_argument("--config", choices=("c2", "c5"), default="c2",
                     help="c2: the headline workload (BASELINE configs[1]); c5: the mixed-shape-class batch of configs[4], 524,288 instances "
                          "split over the ranks present (a rank of a smaller job still holds the share of an 8-GPU job: weak scaling)")
@@ -176,7 +186,7 @@ def main():
     iters = gb.info("iter")
     status = gb.info("status")
     res_max = max(float(gb.info(n).max()) for n in ("res_stat", "res_eq", "res_ineq", "res_comp"))
-    res_indep = float(gb.res_compute().max())
+    res_indep = float(gb.res_compute().max()) if args.full else float("nan")      # a kernel run of its own: --full
 
     if dist is not None:
         stats = torch.tensor([[float(iters.mean()), float(iters.max()), float((status != 0).sum()), res_max, res_indep]],
@@ -189,18 +199,18 @@ def main():
     else:
         mean_iter, max_iter, failures = float(iters.mean()), int(iters.max()), int((status != 0).sum())
 
-    # ---- parity spot check against the oracle (checker only, outside timing) ----
+    # ---- parity spot check against the oracle (checker only, outside timing; --full) ----
     err = None
-    if args.check > 0:
+    if args.full and args.check > 0:
         err = oracle_error(gb, lambda i: lqr_instance_qp(data, i, N), np.linspace(0, B - 1, args.check).astype(int), N, tight=False)["same_tol_max"]
 
     # ---- gather of the full solution payload + statistics over RCCL/xGMI, outside the timed region, LAST: everything the line
-    # reports is in hand by then (guarded_gather) ----
+    # reports is in hand by then (guarded_gather; --full) ----
     def the_gather():
         return gather_solutions(gb, dist, rank, world)       # device buffers, library collective (no host bounce)
 
     if rank != 0:
-        _, gerr = guarded_gather(the_gather, world)
+        _, gerr = guarded_gather(the_gather, world) if args.full else (None, None)
         leave_after_stuck_gather(gerr)
         if dist is not None:
             dist.destroy_process_group()
@@ -245,8 +255,6 @@ def main():
                    "batch_per_gpu": B, "global_batch": world * B, "parallelism": f"instance-sharded x{world}",
                    "kernel": gb.kernel_name, "commit": git_head()},
         "ipm": {"mean_iter": mean_iter, "max_iter": max_iter, "failures": failures, "max_kkt_residual": res_max,
-                "max_kkt_residual_independent": res_indep,
-                "max_rel_primal_err_vs_oracle": err, "oracle_checked_instances": args.check,
                 "launches_per_step": int(gb.scalar("launches")),
                 # the structural waste of one instance per lane: a wave streams its tiles until its LAST lane has converged.
                 # iter_hist[j] = instances (this rank) that took j iterations; wave_max_iter_mean = mean over the 64-instance tiles
@@ -259,35 +267,39 @@ def main():
         "gather_ms": None,
         "gather": None,
     }
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(data, N, min(args.cpu_sample, B))
-        if args.check > 0:
-            # max relative primal error of the GPU solution against the oracle over the whole CPU sample
-            xs = [gb.get("x", k) for k in range(N + 1)]
-            us = [gb.get("u", k) for k in range(N)]
-            err_s = 0.0
-            for i, o in enumerate(cpu_baseline.solved):
-                for k in range(N + 1):
-                    r = o.get(k, "x")
-                    err_s = max(err_s, float(np.max(np.abs(xs[k][i] - r) / np.maximum(1.0, np.abs(r)))))
-                    if k < N:
-                        r = o.get(k, "u")
-                        err_s = max(err_s, float(np.max(np.abs(us[k][i] - r) / np.maximum(1.0, np.abs(r)))))
-            out["ipm"]["max_rel_primal_err_vs_oracle"] = max(err, err_s)
-            out["ipm"]["oracle_checked_instances"] = args.check + len(cpu_baseline.solved)
-        cpu_baseline.solved = None
-    if world == 1 and args.check_configs and not args.no_configs:
-        idx = np.unique(np.linspace(0, B - 1, args.check_configs).astype(int))
-        oe = oracle_error(gb, lambda i: lqr_instance_qp(data, i, N), idx, N)
-        out["ipm"]["oracle_check"] = oe
-        out["ipm"]["max_rel_primal_err_vs_oracle"] = max(out["ipm"]["max_rel_primal_err_vs_oracle"] or 0.0, oe["same_tol_max"])
-        out["ipm"]["oracle_checked_instances"] = int(out["ipm"]["oracle_checked_instances"]) + int(idx.size)
-    if world == 1 and not args.no_configs:
-        out["configs"] = other_configs(gb, data, args)
-        out["configs"]["boundary_C3"] = boundary_c3(args.boundary_n)
-    gather, gerr = guarded_gather(the_gather, world)
-    out["gather_ms"] = gather["ms"] if gather else None
-    out["gather"] = gather if gather or not gerr else {"ranks": world, "error": gerr}
+    # ---- --full: what the headline figure does not need, after the line's own figures are in hand ----
+    gerr = None
+    if args.full:
+        out["ipm"].update({"max_kkt_residual_independent": res_indep, "max_rel_primal_err_vs_oracle": err, "oracle_checked_instances": args.check})
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(data, N, min(args.cpu_sample, B))
+            if args.check > 0:
+                # max relative primal error of the GPU solution against the oracle over the whole CPU sample
+                xs = [gb.get("x", k) for k in range(N + 1)]
+                us = [gb.get("u", k) for k in range(N)]
+                err_s = 0.0
+                for i, o in enumerate(cpu_baseline.solved):
+                    for k in range(N + 1):
+                        r = o.get(k, "x")
+                        err_s = max(err_s, float(np.max(np.abs(xs[k][i] - r) / np.maximum(1.0, np.abs(r)))))
+                        if k < N:
+                            r = o.get(k, "u")
+                            err_s = max(err_s, float(np.max(np.abs(us[k][i] - r) / np.maximum(1.0, np.abs(r)))))
+                out["ipm"]["max_rel_primal_err_vs_oracle"] = max(err, err_s)
+                out["ipm"]["oracle_checked_instances"] = args.check + len(cpu_baseline.solved)
+            cpu_baseline.solved = None
+        if world == 1 and args.check_configs and not args.no_configs:
+            idx = np.unique(np.linspace(0, B - 1, args.check_configs).astype(int))
+            oe = oracle_error(gb, lambda i: lqr_instance_qp(data, i, N), idx, N)
+            out["ipm"]["oracle_check"] = oe
+            out["ipm"]["max_rel_primal_err_vs_oracle"] = max(out["ipm"]["max_rel_primal_err_vs_oracle"] or 0.0, oe["same_tol_max"])
+            out["ipm"]["oracle_checked_instances"] = int(out["ipm"]["oracle_checked_instances"]) + int(idx.size)
+        if world == 1 and not args.no_configs:
+            out["configs"] = other_configs(gb, data, args)
+            out["configs"]["boundary_C3"] = boundary_c3(args.boundary_n)
+        gather, gerr = guarded_gather(the_gather, world)
+        out["gather_ms"] = gather["ms"] if gather else None
+        out["gather"] = gather if gather or not gerr else {"ranks": world, "error": gerr}
     emit(out, args)
     leave_after_stuck_gather(gerr)
     if dist is not None:

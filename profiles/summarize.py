@@ -101,7 +101,7 @@ def sections(fetch_db, write_db, commit=None):
     import json
     import re
     out = {"_note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate counter-only passes over `bench.py --steps 1 "
-                    "--warmup 0 --no-cpu-baseline --check 0 --check-configs 0` (configuration legs included); bytes = "
+                    "--warmup 0 --full --no-cpu-baseline --check 0 --check-configs 0` (configuration legs included); bytes = "
                     "(2*FETCH_SIZE + WRITE_SIZE) * 1024 per MI355X_MICROARCH.md (HBM section).  Per section (marker id) and "
                     "kernel: launches, average over the launches that carry work (> 1 % of the largest) and the largest.",
            "_commit": commit, "_src_hash": kernel_src_hash(), "sections": {}}

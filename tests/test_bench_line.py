@@ -82,3 +82,28 @@ def test_gather_guard_reports_instead_of_hanging():
     assert v is None and "ncclCommInitRank" in e
     line = bench.compact_line({"metric": "m", "value": 1.0, "gather": {"ranks": 2, "error": e}})
     assert json.loads(line)["gather"]["error"] == e
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_full_adds_the_rest(tmp_path):
+    """A plain run prints the headline figure of its timed steps and nothing that takes work of its own; --full adds the oracle
+    spot check, the independent KKT residual and the solutions gather (its configuration legs and CPU baseline take minutes and
+    are switched off here)"""
+    import subprocess
+
+    def run(*extra):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "2048", "--steps", "2", "--warmup", "1",
+                              "--detail-file", str(tmp_path / "detail.json"), *extra], stdout=subprocess.PIPE, check=True, timeout=600)
+        return strict_loads(out.stdout.decode().strip().splitlines()[-1])
+
+    plain = run()
+    for k in HEAD + ("ipm", "roofline"):
+        assert k in plain, k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["ipm"]["failures"] == 0
+    assert not {"cpu_baseline", "configs", "gather"} & set(plain)
+    assert not {"max_rel_primal_err_vs_oracle", "oracle_checked_instances", "max_kkt_residual_independent"} & set(plain["ipm"])
+    full = run("--full", "--no-configs", "--no-cpu-baseline", "--check", "4")
+    assert full["ipm"]["oracle_checked_instances"] == 4 and full["ipm"]["max_rel_primal_err_vs_oracle"] <= 1e-8
+    assert full["ipm"]["max_kkt_residual_independent"] <= 1e-7
+    assert full["gather"]["ranks"] == 1 and full["gather"]["slice_matches_getters"]
+    assert not {"cpu_baseline", "configs"} & set(full)

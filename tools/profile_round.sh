@@ -27,13 +27,13 @@ f=$(find /tmp/pmc_f -name "*.db" | head -1); w=$(find /tmp/pmc_w -name "*.db" | 
 python $root/profiles/summarize.py traffic $f $w $commit > $out/${tag}_pmc_traffic.json
 cp $out/${tag}_pmc_traffic.json $root/profiles/${tag}_pmc_traffic.json   # the bench below reads the file of THIS build
 if [ "$3" = "full" ]; then
-    rocprofv3 --kernel-trace --stats -d /tmp/prof_cfg -- python $root/bench.py --steps 1 --warmup 1 --no-cpu-baseline --check 0 --check-configs 0 > $out/${tag}_bench_configs_under_rocprof.json 2> $out/${tag}_rocprof_cfg.log
+    rocprofv3 --kernel-trace --stats -d /tmp/prof_cfg -- python $root/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --check 0 --check-configs 0 > $out/${tag}_bench_configs_under_rocprof.json 2> $out/${tag}_rocprof_cfg.log
     # (the boundary leg of the bench runs a child process with a trace database of its own: the bench's is the largest)
     db=$(ls -S $(find /tmp/prof_cfg -name "*.db") | head -1)
     python $root/profiles/summarize.py kernel $db > $out/${tag}_config_kernel_stats.txt
     # HBM traffic of the configuration legs: the same two counter-only passes over the bench WITH its configuration legs;
     # bench.py brackets every configuration's timed solves with marker launches, summarize.py cuts the sequence there
-    cfgq="--steps 1 --warmup 0 --no-cpu-baseline --check 0 --check-configs 0"
+    cfgq="--full --steps 1 --warmup 0 --no-cpu-baseline --check 0 --check-configs 0"
     rm -rf /tmp/pmc_cf /tmp/pmc_cw
     rocprofv3 --pmc FETCH_SIZE -d /tmp/pmc_cf -- python $root/bench.py $cfgq > /dev/null 2> $out/${tag}_pmc_cf.log
     rocprofv3 --pmc WRITE_SIZE -d /tmp/pmc_cw -- python $root/bench.py $cfgq > /dev/null 2> $out/${tag}_pmc_cw.log
@@ -45,4 +45,4 @@ if [ "$3" = "full" ]; then
     cp $out/${tag}_mfma_util.json $root/profiles/${tag}_mfma_util.json
 fi
 # the full object goes to <tag>_bench.json (what the tests and bench.py's readers load), the line the driver parses to <tag>_bench_line.json
-cd $root && python bench.py --detail-file $out/${tag}_bench.json 2> $out/${tag}_bench_err.log | tail -1 > $out/${tag}_bench_line.json
+cd $root && python bench.py --full --detail-file $out/${tag}_bench.json 2> $out/${tag}_bench_err.log | tail -1 > $out/${tag}_bench_line.json
