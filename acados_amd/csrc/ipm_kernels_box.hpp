@@ -219,6 +219,20 @@ __device__ static inline Acc acc_at(GArr arr, size_t e0, int i)
 #define GQP_KB_FOLD 1
 #endif
 
+/* 1: the affine forward sweep (kb_forward<CORR = false>) computes no dpi and, behind stage 0, takes the state part of the step
+ * from the dynamics: it never uses the Lxx block of the factor nor lx there, and does not load them -- 44 of the 191 doubles a
+ * C2 stage loads, 1.18 GB of 5.27 GB per full launch.  Stage 0 solves for dx_0 and keeps the full loads: ONE wave-uniform
+ * branch per stage around the extra loads; the entries not read are 0.0 and feed only what the `first ?` selects discard,
+ * so the iterates stay bit for bit.  Not where box rows sit on the states (XBOX: those instantiations are at the register
+ * limit and the branch costs them scratch).  0: the full loads at every stage (the cross-check:
+ * make variant TAG=noslim DEFS=-DGQP_KB_AFF_SLIM=0, tools/variant_rate.py c2 libacados_amd_qp_noslim.so).
+ * (Measured with it and NOT taken, profiles/NOTES.md "Box sweeps": every load of a stage of kb_forward<CORR = false> / kb_backrhs
+ * requested in one burst in front of the first use, and the loads in ordered groups one step ahead of the arithmetic with the
+ * next stage's first group fetched across the stage boundary -- both slower than the schedule hipcc finds by itself.) */
+#ifndef GQP_KB_AFF_SLIM
+#define GQP_KB_AFF_SLIM 1
+#endif
+
 #define GQP_ROW_CHUNK 4  /* rows of [B A]' fetched per load phase in kb_factor */
 #define GQP_HROW_CHUNK 3 /* Hessian rows fetched per load phase in kb_factor */
 
@@ -629,12 +643,21 @@ template <int NX, int NU, bool XBOX, bool CORR>
 __global__ void __launch_bounds__(64) kb_forward(GqpDev D, GqpOpts O, int redo)
 {
     constexpr int n = NX + NU, NP = n * (n + 1) / 2, NB = XBOX ? n : NU;
+    constexpr bool SLIM = GQP_KB_AFF_SLIM && !CORR && !XBOX;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= D.B) return;
     const bool run = D.status[i] == GQP_RUNNING;
     if (redo ? !(run && D.alpha[i] < 0.0) : !GQP_WAVE_ANY(run)) return;
     const double smu = CORR ? D.smu[i] : 0.0;
     const double pscale = (CORR && !redo) ? 1.0 : 0.0;
+    /* SLIM: what the epilogue reads is fetched here and what it writes is addressed here, in vector registers -- the pointers it
+     * held in scalar registers across the stage loop were spilled beside the stage's buffer resources */
+    const double mu_in = SLIM ? D.mu[i] : 0.0;
+    const int it_in = SLIM ? D.iter[i] : 0;
+    double *p_smu = D.smu + i, *p_alpha = D.alpha + i;
+    double *st_in = (SLIM && i < D.stat_inst && it_in + 1 < D.stat_rows) ? D.stat + (size_t) (it_in + 1) * GQP_STAT_COLS * D.stat_inst + i : nullptr;
+    int sti = D.stat_inst;
+    if (SLIM) { GQP_OPAQUE(p_smu); GQP_OPAQUE(p_alpha); GQP_OPAQUE(st_in); GQP_OPAQUE(sti); }
 
     double alpha = 1.0, S0 = 0.0, S1 = 0.0, S2 = 0.0;
     int nact = 0;
@@ -649,8 +672,24 @@ __global__ void __launch_bounds__(64) kb_forward(GqpDev D, GqpOpts O, int redo)
         const int nbg = S.nb;
 
         double L[NP], l[n], bat[n * NX], rbn[NX];
-        UNROLL for (int e = 0; e < NP; e++) L[e] = ACC(D.Lf, 0).ld(k * NP + e);
-        UNROLL for (int j = 0; j < n; j++) l[j] = ACC(D.lf, 0).ld(k * n + j);
+        if (SLIM)
+        {
+            /* the NU leading columns of L and l[0, NU) are all the input part of the step needs; Lxx and lx only at stage 0 */
+            UNROLL for (int r = 0; r < n; r++)
+                UNROLL for (int c = 0; c <= r; c++) L[PK(r, c)] = c < NU ? ACC(D.Lf, 0).ld(k * NP + PK(r, c)) : 0.0;
+            UNROLL for (int j = 0; j < n; j++) l[j] = j < NU ? ACC(D.lf, 0).ld(k * n + j) : 0.0;
+            if (k == 0)
+            {
+                UNROLL for (int r = NU; r < n; r++)
+                    UNROLL for (int c = NU; c <= r; c++) L[PK(r, c)] = ACC(D.Lf, 0).ld(k * NP + PK(r, c));
+                UNROLL for (int j = NU; j < n; j++) l[j] = ACC(D.lf, 0).ld(k * n + j);
+            }
+        }
+        else
+        {
+            UNROLL for (int e = 0; e < NP; e++) L[e] = ACC(D.Lf, 0).ld(k * NP + e);
+            UNROLL for (int j = 0; j < n; j++) l[j] = ACC(D.lf, 0).ld(k * n + j);
+        }
         UNROLL for (int e = 0; e < n * NX; e++) bat[e] = ACC(D.BAt, 0).ld(k * n * NX + e);
         UNROLL for (int c = 0; c < NX; c++) rbn[c] = ACC(D.rb, 0).ld(k * NX + c);
         double laml[NB], lamu[NB], tl[NB], tu[NB], rdl[NB], rdu[NB], pl[NB], pu[NB];
@@ -756,19 +795,19 @@ __global__ void __launch_bounds__(64) kb_forward(GqpDev D, GqpOpts O, int redo)
         }
     }
 
-    const int it = D.iter[i];
-    double *st = (i < D.stat_inst && it + 1 < D.stat_rows) ? D.stat + (size_t) (it + 1) * GQP_STAT_COLS * D.stat_inst + i : nullptr;
+    const int it = SLIM ? it_in : D.iter[i];
+    double *st = SLIM ? st_in : (i < D.stat_inst && it + 1 < D.stat_rows) ? D.stat + (size_t) (it + 1) * GQP_STAT_COLS * D.stat_inst + i : nullptr;
     if (!CORR)
     {
         if (!run) return;
         /* mu_aff = sum (lam + a dlam)(t + a dt) / nact, expanded in the three running sums */
-        const double mu = D.mu[i];
+        const double mu = SLIM ? mu_in : D.mu[i];
         const double mu_aff = nact > 0 ? (S0 + alpha * S1 + alpha * alpha * S2) / nact : 0.0;
         double sigma = mu > 0.0 ? mu_aff / mu : 0.0;
         sigma = sigma * sigma * sigma;
-        D.smu[i] = sigma * mu;
-        D.alpha[i] = alpha;
-        if (st) { st[0] = alpha; st[1 * D.stat_inst] = alpha; st[2 * D.stat_inst] = mu_aff; st[3 * D.stat_inst] = sigma; }
+        *p_smu = sigma * mu;
+        *p_alpha = alpha;
+        if (st) { st[0] = alpha; st[1 * sti] = alpha; st[2 * sti] = mu_aff; st[3 * sti] = sigma; }
         return;
     }
     const double alpha_aff = dabs(D.alpha[i]);
