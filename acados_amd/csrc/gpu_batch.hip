@@ -228,6 +228,9 @@ struct ocp_qp_gpu_batch
     int tail_max = 12288;                /* switch to it when at most this many instances (and 1 / tail_div of the level) remain; 0 = off */
     int tail_div = 4;
     int n_tail_switches = 0;
+    /* held dynamics of the one-instance-per-lane box sweeps (ipm_kernels_box.hpp; run_ipm) */
+    int hold_dynamics = 1;               /* option: 1 = tiles whose [B A]' is found stage-invariant keep it in registers, 0 = never */
+    int n_tiles_invariant = 0;           /* tiles found so by the last solve */
     /* solution sensitivities / factor at the solution */
     bool factor_stale = false;           /* the last solve finished instances on a sub-level: Lf of the root is not theirs */
     bool sens_open = false;              /* seeds are being collected (rg, rb, rd hold seeds, not residuals) */
@@ -319,7 +322,7 @@ void opts_default(GqpOpts &o)
     o.mu0 = 1e0;
     o.tol_stat = 1e-6; o.tol_eq = 1e-8; o.tol_ineq = 1e-8; o.tol_comp = 1e-8;
     o.alpha_min = 1e-8; o.tau_min = 0.0; o.lam_min = 1e-16; o.t_min = 1e-16; o.reg_prim = 1e-15;
-    o.iter_max = 50; o.pred_corr = 1; o.cond_pred_corr = 1; o.warm_start = 0; o.ext_update = 0;
+    o.iter_max = 50; o.pred_corr = 1; o.cond_pred_corr = 1; o.warm_start = 0; o.ext_update = 0; o.hold = 0;
     o.t0_init = 2; /* acados_ocp_options.py:1128-1143: the default is the residual-based start */
 }
 
@@ -576,6 +579,7 @@ void finalize_structure(ocp_qp_gpu_batch *b)
     D.apend = dalloc<double>(b, Bp);
     D.iter = dalloc<int>(b, Bp); D.status = dalloc<int>(b, Bp);
     D.n_active = dalloc<int>(b, 1);
+    D.tile_inv = dalloc<int>(b, (size_t) Bp / 64);
     b->stat_inst = b->B < 64 ? b->B : 64;
     b->stat_rows = 0;
     D.stat = nullptr; D.stat_inst = 0; D.stat_rows = 0;
@@ -1242,6 +1246,7 @@ try
     }
     else if (!strcmp(f, "compact_min")) b->compact_min = *i;
     else if (!strcmp(f, "tail_max")) b->tail_max = *i;
+    else if (!strcmp(f, "hold_dynamics")) b->hold_dynamics = *i != 0;
     else if (!strcmp(f, "tail_div")) b->tail_div = *i < 1 ? 1 : *i;
     else if (!strcmp(f, "solve_max")) b->solve_max = *i;
     else if (!strcmp(f, "cond_N"))
@@ -1644,6 +1649,13 @@ static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, ocp_qp_gpu_batch *c
  * of the level is still iterating, the survivors (QP data + iterate, ~98 KB each for C2) are
  * copied into a dense sub-batch, the loop continues there (recursively), and the results are
  * scattered back.  Per-instance arithmetic is unchanged, so results are bit-identical.
+ *
+ * Held dynamics (ipm_kernels_box.hpp): the ROOT level zeroes GqpDev::tile_inv in front of its loop and behind it, lets its first
+ * affine forward sweep count the lanes with stage-invariant [B A]' into it (GqpOpts::hold bit 1) and runs every sweep of its loop
+ * with GqpOpts::hold bit 0.  The counters are read back behind that sweep and counted at the loop's next synchronisation
+ * ("tiles_invariant").  Sub-levels never set either bit and their counters stay zero: nothing is copied by compact_into.  Every
+ * other launch of these kernels (sensitivities, a later solve, the polish pass -- a root loop of its own, which detects again)
+ * finds the counters at zero.
  */
 /* side -> (stage, activity bit) of k_step_update, once per batch */
 static const int *side_map(ocp_qp_gpu_batch *b)
@@ -1683,6 +1695,14 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
      * GEN always, box classes up to 16,384 instances from N = 50 on.  ACADOS_AMD_EXT_UPDATE=0 / 1 forces the pass / the launch */
     const char *eext = getenv("ACADOS_AMD_EXT_UPDATE");
     const bool ext_update = b->w16 && (eext ? atoi(eext) != 0 : (b->w16_ng > 0 || (b->B <= 16384 && b->N >= 50)));
+    const bool hold = b == root && root->hold_dynamics && b->use_box && !b->wpi && !b->w16;
+    O.hold = hold ? 1 : 0;
+    bool detect = hold, counted = !hold; /* the first affine sweep detects; its counters are summed once they have arrived */
+    if (b == root)
+    {
+        root->n_tiles_invariant = 0;
+        HIPCHK(hipMemsetAsync(D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+    }
     GqpOpts Oc = O; /* options of the corrector-sweep launches */
     Oc.ext_update = ext_update ? 1 : 0;
     const int *smap = ext_update ? side_map(b) : nullptr;
@@ -1701,7 +1721,11 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         root->n_single_launch++;
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (*b->h_nact <= 0) return;
+        if (*b->h_nact <= 0)
+        {
+            if (b == root) HIPCHK(hipMemsetAsync(D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+            return;
+        }
         /* (never taken: a row leaves the kernel only with its instance out of the RUNNING state) */
     }
     for (;; it++)
@@ -1713,6 +1737,13 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         const int nact = *b->h_nact;
+        if (!detect && !counted)
+        {
+            int full = 0;
+            for (int q = 0; q < (b->B + 63) / 64; q++) full += b->h_ints[q] == std::min(64, b->B - 64 * q);
+            root->n_tiles_invariant = full;
+            counted = true;
+        }
         if (root->print_level > 1) printf("acados_amd: ipm iter %d level size %d active %d\n", it, b->B, nact);
         if (nact <= 0 || it > O.iter_max) break;
         if (use_perm && nact >= 1 && 6 * nact <= 5 * b->w16_slots)
@@ -1748,8 +1779,17 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
             break;
         }
         if (b == root) prof.begin(2, s);
-        GQP_SWEEP_LAUNCH(b, K.faff, b->shmem_fwd, s, D, O, 0);
+        {
+            GqpOpts Oa = O;
+            if (detect) Oa.hold |= 2;
+            GQP_SWEEP_LAUNCH(b, K.faff, b->shmem_fwd, s, D, Oa, 0);
+        }
         if (b == root) prof.end(s);
+        if (detect)
+        {
+            HIPCHK(hipMemcpyAsync(b->h_ints, D.tile_inv, sizeof(int) * (size_t) (b->Bp / 64), hipMemcpyDeviceToHost, s));
+            detect = false;
+        }
         if (b == root) prof.begin(3, s);
         GQP_SWEEP_LAUNCH(b, K.rhs, b->shmem, s, D, O, 0);
         if (b == root) prof.end(s);
@@ -1772,6 +1812,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         }
     }
     b->w16_slots = b->B; /* launches outside this loop (sensitivity passes) cover every instance again */
+    if (b == root) HIPCHK(hipMemsetAsync(D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
 }
 
 /*
@@ -1821,7 +1862,9 @@ static void polish_pass(ocp_qp_gpu_batch *b, Prof &prof, hipStream_t s)
     const GqpOpts Oeff = effective_opts(keep, b);
     b->O.tau_min = Oeff.tau_min; /* the barrier floor of the solve (derived from ITS tol_comp) */
     D.stat_inst = 0;             /* the statistics table keeps the solve's rows */
+    const int keep_inv = b->n_tiles_invariant; /* ("tiles_invariant" speaks of the solve) */
     run_ipm(b, b, prof, s, 0);
+    b->n_tiles_invariant = keep_inv;
     b->O = keep;
     D.stat_inst = keep_stat;
     hipLaunchKernelGGL(gqp::k_polish_restore, g64, blk, 0, s, D, Oeff, b->d_pol_status, b->d_pol_iter, b->d_pol_sc, b->d_pol_flag, b->d_pol_cnt + 1);
@@ -2541,6 +2584,7 @@ try
     if (!strcmp(f, "compactions")) return (double) b->n_compactions;
     if (!strcmp(f, "w16_tiles")) return (double) b->w16_tiles;
     if (!strcmp(f, "tail_switches")) return (double) b->n_tail_switches;
+    if (!strcmp(f, "tiles_invariant")) return (double) b->n_tiles_invariant;
     if (!strcmp(f, "single_launch_solves")) return (double) b->n_single_launch;
     if (!strcmp(f, "cond_N_active")) return b->pcond_state == 1 ? (double) b->child->N : (double) b->N;
     if (!strcmp(f, "tol_comp_soft_scale")) return b->tol_comp_soft_scale;

@@ -57,6 +57,9 @@ struct GqpOpts
                     (acados_ocp_options.py:1128-1143); 0 / 1 leave the primal iterate at zero */
     int ext_update; /* set by the host loop for the launch-per-sweep corrector sweeps of the sixteen-lanes families: the sweep leaves
                        its step length in GqpDev::apend and the step is applied by k_step_update, a launch of its own (ipm_kernels.hpp) */
+    int hold;       /* set by the host loop, read by the one-instance-per-lane box sweeps (ipm_kernels_box.hpp, "held dynamics"): bit 0 --
+                       tiles whose counter in GqpDev::tile_inv is full keep [B A]' in registers across the stages; bit 1 -- this launch
+                       (the first affine forward sweep of the root loop) fills the counters.  0 everywhere else */
 };
 
 /* One per-instance HBM array: `E` elements per instance, stored WAVE-TILED,
@@ -117,6 +120,9 @@ struct GqpDev
                       update"); 0 = nothing pending.  Other families apply their steps themselves and leave it 0 */
     int *iter, *status;
     int *n_active; /* single counter: instances still iterating */
+    int *tile_inv; /* [Bp / 64] per 64-instance tile: lanes whose [B A]' is bit for bit the same at every stage k = 0 .. N-1, counted
+                      by the first affine forward sweep of the root loop and zero outside that loop (ipm_kernels_box.hpp, "held
+                      dynamics"); sub-levels keep theirs at zero */
     double *stat;  /* [stat_rows][STAT_COLS][Bp_stat] for the first stat_inst instances */
     int stat_inst, stat_rows;
     /* sixteen-lanes-per-instance sweeps: row slot -> instance.  Null: slot = instance.  Otherwise the n_perm instances that

@@ -15,7 +15,10 @@
  *   - no IEEE division/sqrt sequences: v_rcp_f64 / v_rsq_f64 + two Newton steps;
  *   - fewer bytes: rm is recomputed (lam*t), the affine sweep stores only dlam*dt (what the
  *     Mehrotra corrector needs) and neither dux nor dpi; mu_aff comes from three running sums
- *     instead of a second pass over lam,t,dlam,dt.
+ *     instead of a second pass over lam,t,dlam,dt;
+ *   - fewer bytes again where the dynamics are the same at every stage: the two forward sweeps keep [B A]' in registers
+ *     across the stages of a tile found stage-invariant (88 of the 153 / 228 doubles a C2 stage of these sweeps moves), see
+ *     "HELD DYNAMICS" below; kb_factor (row chunks at its register ceiling) and kb_backrhs fetch the block as before.
  * Equality-flagged rows (idxe) are not IPM rows here; their multipliers are recovered from
  * stationarity in kb_finalize.
  */
@@ -60,6 +63,19 @@ __device__ static inline int popc64(uint64_t x)
     return __popcll(x);
 #else
     return __builtin_popcountll(x);
+#endif
+}
+
+/* the 64-bit pattern of a double: what "the same value" means where held registers stand in for loads (-0.0 differs from
+ * +0.0, NaN patterns compare like any others) */
+__device__ static inline uint64_t dbits(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_bit_cast(uint64_t, x);
+#else
+    uint64_t u;
+    memcpy(&u, &x, sizeof u);
+    return u;
 #endif
 }
 
@@ -232,6 +248,34 @@ __device__ static inline Acc acc_at(GArr arr, size_t e0, int i)
 #ifndef GQP_KB_AFF_SLIM
 #define GQP_KB_AFF_SLIM 1
 #endif
+
+/* HELD DYNAMICS.  A plant with constant dynamics has the same [B A]' at every stage k = 0 .. N-1 of an instance, and the two
+ * forward sweeps (kb_forward<CORR = false / true>) then fetch the same n * NX doubles at every stage: 88 of the 153 / 228 a C2
+ * stage moves.  Where the block fits beside the stage (kb_hold: no scratch, no spill -- read from the compiler's remarks) it is
+ * a loop-carried register array, fetched at the first stage and at the zero slot N only, as long as EVERY lane of the tile has
+ * stage-invariant dynamics; otherwise at every stage, the code path of before.  The registers hold the very values the loads
+ * would have returned: results are bit for bit the same.
+ *   Detection costs no memory traffic: the first affine forward sweep of the root loop (GqpOpts::hold bit 1) fetches every
+ * stage's block anyway and compares it, row by row and on the 64-bit patterns, with the one it holds from the stage before
+ * (k = 1 .. N-1); the lanes whose stages all agree are counted into GqpDev::tile_inv.  A tile is held when its count equals the
+ * instances it carries.  The host zeroes the counters in front of and behind the root loop (gpu_batch.hip, run_ipm): no
+ * other launch of these kernels ever sees a flag older than the data.  GqpOpts::hold bit 0 off (option hold_dynamics 0, every
+ * sub-level): every tile fetches at every stage.
+ *   NOT kb_backrhs, whose code is untouched: holding its block was measured twice and cost the tiles that fetch at every stage
+ * (time-varying dynamics) -- the block fetched into a carried array under a branch at the top of the stage + 0.04 ms per launch,
+ * the product branched on the flag 2.06 against 1.11 ms per launch (profiles/NOTES.md, "stage-invariant [B A]'"). */
+template <int NX, int NU, bool XBOX>
+constexpr bool kb_hold()
+{
+    return !XBOX && (NX + NU) * NX <= 88;
+}
+/* does this wave hold its block? (wave-uniform, and provably so) */
+__device__ static inline bool kb_tile_inv(const GqpDev &D, const GqpOpts &O)
+{
+    if (!(O.hold & 1)) return false;
+    const int left = D.B - (int) blockIdx.x * 64;
+    return uni(D.tile_inv[blockIdx.x]) == (left < 64 ? left : 64);
+}
 
 #define GQP_ROW_CHUNK 4  /* rows of [B A]' fetched per load phase in kb_factor */
 #define GQP_HROW_CHUNK 3 /* Hessian rows fetched per load phase in kb_factor */
@@ -659,10 +703,21 @@ __global__ void __launch_bounds__(64) kb_forward(GqpDev D, GqpOpts O, int redo)
     int sti = D.stat_inst;
     if (SLIM) { GQP_OPAQUE(p_smu); GQP_OPAQUE(p_alpha); GQP_OPAQUE(st_in); GQP_OPAQUE(sti); }
 
+    /* held dynamics (see kb_hold): `inv` -- this tile keeps its block across the stages; `detect` -- this launch counts the lanes
+     * whose block is the same at every stage (the counters are zero then, so nothing is held while it is found out) */
+    constexpr bool HOLD = kb_hold<NX, NU, XBOX>();
+    const bool inv = HOLD && kb_tile_inv(D, O);
+    const bool detect = HOLD && !CORR && !redo && (O.hold & 2);
+    uint64_t differs = 0;
+    int *p_cnt = HOLD ? D.tile_inv + blockIdx.x : nullptr; /* (in vector registers, like the epilogue's other addresses) */
+    if (HOLD && !CORR) GQP_OPAQUE(p_cnt);
+
     double alpha = 1.0, S0 = 0.0, S1 = 0.0, S2 = 0.0;
     int nact = 0;
     double dx[NX];
     UNROLL for (int c = 0; c < NX; c++) dx[c] = 0.0;
+    double bat[n * NX]; /* HOLD: carried from stage to stage; otherwise written in full by every stage before it is read */
+    if (HOLD) { UNROLL for (int e = 0; e < n * NX; e++) bat[e] = 0.0; }
 
     for (int k = 0; k <= D.N; k++)
     {
@@ -671,7 +726,24 @@ __global__ void __launch_bounds__(64) kb_forward(GqpDev D, GqpOpts O, int redo)
         const uint64_t am = GAT(D.amask, k);
         const int nbg = S.nb;
 
-        double L[NP], l[n], bat[n * NX], rbn[NX];
+        const bool det_k = HOLD && !CORR && detect && k > 0 && k < D.N;
+        if (det_k)
+        {
+            /* a real stage behind the first: row by row against the block held from the stage before, then held itself.  In front
+             * of the stage's other loads, in a block of its own: with those in flight beside the held block and the rows it is
+             * compared with, the kernel spilled 45 vector registers.  One more memory round trip per stage, in this launch only */
+            UNROLL for (int r = 0; r < n; r++)
+            {
+                double row[NX];
+                UNROLL for (int c = 0; c < NX; c++) row[c] = ACC(D.BAt, 0).ld(k * n * NX + r * NX + c);
+                UNROLL for (int c = 0; c < NX; c++)
+                {
+                    differs |= dbits(row[c]) ^ dbits(bat[r * NX + c]);
+                    bat[r * NX + c] = row[c];
+                }
+            }
+        }
+        double L[NP], l[n], rbn[NX];
         if (SLIM)
         {
             /* the NU leading columns of L and l[0, NU) are all the input part of the step needs; Lxx and lx only at stage 0 */
@@ -690,7 +762,10 @@ __global__ void __launch_bounds__(64) kb_forward(GqpDev D, GqpOpts O, int redo)
             UNROLL for (int e = 0; e < NP; e++) L[e] = ACC(D.Lf, 0).ld(k * NP + e);
             UNROLL for (int j = 0; j < n; j++) l[j] = ACC(D.lf, 0).ld(k * n + j);
         }
-        UNROLL for (int e = 0; e < n * NX; e++) bat[e] = ACC(D.BAt, 0).ld(k * n * NX + e);
+        if (!det_k && (!HOLD || !inv || k == 0 || k == D.N))
+        {
+            UNROLL for (int e = 0; e < n * NX; e++) bat[e] = ACC(D.BAt, 0).ld(k * n * NX + e);
+        }
         UNROLL for (int c = 0; c < NX; c++) rbn[c] = ACC(D.rb, 0).ld(k * NX + c);
         double laml[NB], lamu[NB], tl[NB], tu[NB], rdl[NB], rdu[NB], pl[NB], pu[NB];
         UNROLL for (int j = 0; j < NB; j++)
@@ -795,6 +870,16 @@ __global__ void __launch_bounds__(64) kb_forward(GqpDev D, GqpOpts O, int redo)
         }
     }
 
+    if (HOLD && !CORR && detect)
+    {
+        /* finished lanes ride along and count too; lanes past the batch are not here */
+#if defined(__HIP_DEVICE_COMPILE__)
+        const int same = popc64(__builtin_amdgcn_ballot_w64(differs == 0));
+        if (threadIdx.x == 0) *p_cnt = same;
+#else
+        if (differs == 0) *p_cnt += 1; /* (one lane at a time: the contract is the count) */
+#endif
+    }
     const int it = SLIM ? it_in : D.iter[i];
     double *st = SLIM ? st_in : (i < D.stat_inst && it + 1 < D.stat_rows) ? D.stat + (size_t) (it + 1) * GQP_STAT_COLS * D.stat_inst + i : nullptr;
     if (!CORR)
