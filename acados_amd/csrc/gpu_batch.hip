@@ -118,6 +118,20 @@ const PcondzSet g_pcondz_sets[] = {GQP_PCONDZ(8, 3, 5), GQP_PCONDZ(4, 1, 4)};
 
 } // namespace
 
+/* Sub-batches that take instances of a batch over (sub_batch_create / _load / _store below), created on first use:
+ * the still-iterating instances in a dense batch of the same kernel set (next level of run_ipm, capacity <= B/2), and three
+ * wave-per-instance batches at the padded dims: the tail for the last survivors of a one-instance-per-lane level, the one every
+ * ric_alg 0 solve of such a batch is handed to, the one its sensitivities run in slice by slice.  (The condensed batch `child` of
+ * partial condensing is a different QP, not a subset of the instances: not one of them) */
+enum SubRole { SUB_COMPACT, SUB_TAIL, SUB_RIC0, SUB_SENS, SUB_ROLES };
+struct SubBatch
+{
+    ocp_qp_gpu_batch *c = nullptr;
+    int *d_list = nullptr; /* instance index (in the parent) of every slot of `c`; lives as long as the parent */
+    int list_cap = 0;
+    int cap = 0;           /* instances `c` was made for */
+};
+
 struct ocp_qp_gpu_batch
 {
     int B = 0, Bp = 0, N = 0, device = 0;
@@ -219,13 +233,11 @@ struct ocp_qp_gpu_batch
     gqp::PcondMap pmap;
     double time_xcond = 0.0;
     bool lhs_ready = false;         /* condense_lhs done: the next solve only condenses the vector part */
-    /* compaction of the still-iterating instances into a dense sub-batch (see run_ipm) */
-    ocp_qp_gpu_batch *compact = nullptr; /* next level, capacity <= B/2, created on first use */
+    SubBatch sub[SUB_ROLES];
     const KernelSet *force_ks = nullptr; /* sub-batches run the very same kernel set */
     int compact_min = 1 << 30;           /* levels smaller than this are not compacted; off by default: it only
                                             pays once every sweep kernel is bandwidth-bound */
-    ocp_qp_gpu_batch *tail = nullptr;    /* wave-per-instance sub-batch for the last survivors of a one-instance-per-lane level */
-    int tail_max = 12288;                /* switch to it when at most this many instances (and 1 / tail_div of the level) remain; 0 = off */
+    int tail_max = 12288;                /* switch to the tail sub-batch when at most this many instances (and 1 / tail_div of the level) remain; 0 = off */
     int tail_div = 4;
     int n_tail_switches = 0;
     /* held dynamics of the one-instance-per-lane box sweeps (ipm_kernels_box.hpp; run_ipm) */
@@ -236,10 +248,9 @@ struct ocp_qp_gpu_batch
     bool sens_open = false;              /* seeds are being collected (rg, rb, rd hold seeds, not residuals) */
     GArr sfix = {nullptr, 0, 0};         /* derivative of the equality-flagged variables (e.g. x0), [N+2][n] */
     int *d_saved_status = nullptr;
-    ocp_qp_gpu_batch *sens_child = nullptr; /* wave-per-instance sub-batch the sensitivities of a one-instance-per-lane batch run in */
     /* Riccati recursion (option "ric_alg"): 1 square-root (every family), 0 classical (wave-per-instance sweeps only, RIC0 of
      * ipm_kernels_wpi.hpp).  A wave-per-instance-layout batch swaps its kernel set in place (ric1 keeps what it replaced); a
-     * one-instance-per-lane batch hands every solve to ric0_child, a wave-per-instance batch at its padded dims */
+     * one-instance-per-lane batch hands every solve to sub[SUB_RIC0], a wave-per-instance batch at its padded dims */
     int ric_alg = 1;
     struct Ric1
     {
@@ -251,13 +262,6 @@ struct ocp_qp_gpu_batch
         size_t shmem = 0, shmem_fwd = 0, shmem_fact = 0;
         std::string kname;
     } ric1;
-    ocp_qp_gpu_batch *ric0_child = nullptr;
-    int *d_rlist = nullptr; /* 0 .. B-1: the hand-over list of ric0_child */
-    int *d_slist = nullptr;
-    int sens_cap = 0;
-    int tail_cap = 0;
-    int *d_list = nullptr;               /* instance index of every slot of `compact` / `tail` */
-    int list_cap = 0;
     int n_compactions = 0;
     /* KKT residuals of the current (data, iterate) on demand (res_kernels.hpp) */
     gqp::ResOut R = {{nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, nullptr, 0};
@@ -1086,10 +1090,7 @@ try
     for (hipEvent_t e : b->prof_ev) (void) hipEventDestroy(e);
     (void) hipStreamDestroy(b->stream);
     if (b->child) ocp_qp_gpu_batch_destroy(b->child);
-    if (b->compact) ocp_qp_gpu_batch_destroy(b->compact);
-    if (b->tail) ocp_qp_gpu_batch_destroy(b->tail);
-    if (b->sens_child) ocp_qp_gpu_batch_destroy(b->sens_child);
-    if (b->ric0_child) ocp_qp_gpu_batch_destroy(b->ric0_child);
+    for (SubBatch &sb : b->sub) ocp_qp_gpu_batch_destroy(sb.c);
     delete b;
 }
 catch (const gqp_hip_failure &) {}
@@ -1173,10 +1174,7 @@ catch (const gqp_hip_failure &) { return -1; }
 static void ric_switch(ocp_qp_gpu_batch *b, int v)
 {
     b->ric_alg = v;
-    if (b->compact) { ocp_qp_gpu_batch_destroy(b->compact); b->compact = nullptr; }
-    if (b->tail) { ocp_qp_gpu_batch_destroy(b->tail); b->tail = nullptr; }
-    if (b->sens_child) { ocp_qp_gpu_batch_destroy(b->sens_child); b->sens_child = nullptr; }
-    if (b->ric0_child) { ocp_qp_gpu_batch_destroy(b->ric0_child); b->ric0_child = nullptr; }
+    for (SubBatch &sb : b->sub) { ocp_qp_gpu_batch_destroy(sb.c); sb.c = nullptr; } /* (the lists stay) */
     b->factor_stale = true;
     b->sens_open = false;
     if (b->child) ric_switch(b->child, v); /* the condensed batch of partial condensing */
@@ -1194,9 +1192,9 @@ static void set_stream_priority(ocp_qp_gpu_batch *b, int prio)
     HIPCHK(hipStreamDestroy(b->stream));
     HIPCHK(hipStreamCreateWithPriority(&b->stream, hipStreamDefault, p));
     b->stream_priority = prio;
-    /* sub-batches that exist already and launch on streams of their own (the sensitivity slices, the condensed batch) follow;
-     * the ones created later take the priority at creation (round-3 advice) */
-    if (b->sens_child) set_stream_priority(b->sens_child, prio);
+    /* sub-batches that exist already follow (the classical-Riccati one, the sensitivity slices and the condensed batch launch on
+     * streams of their own); the ones created later take the priority at creation (round-3 advice) */
+    for (SubBatch &sb : b->sub) if (sb.c) set_stream_priority(sb.c, prio);
     if (b->child) set_stream_priority(b->child, prio);
 }
 
@@ -1241,8 +1239,7 @@ try
     {
         /* several batches solved concurrently from host threads (the C5 classes): the long ones on a high-priority
          * stream (negative value, clamped to the device's range) are dispatched first, the short ones fill the gaps */
-        set_stream_priority(b, *i); /* (the condensed batch and the sensitivity slices follow inside) */
-        if (b->tail) set_stream_priority(b->tail, *i);
+        set_stream_priority(b, *i); /* (every sub-batch and the condensed batch follow inside) */
     }
     else if (!strcmp(f, "compact_min")) b->compact_min = *i;
     else if (!strcmp(f, "tail_max")) b->tail_max = *i;
@@ -1639,8 +1636,8 @@ struct Prof
     }
 };
 
-static void compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, int nact, hipStream_t s, bool tail);
-static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, ocp_qp_gpu_batch *c, int it0);
+static ocp_qp_gpu_batch *compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, hipStream_t s, SubRole role);
+static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, SubRole role, int it0);
 
 /*
  * One level of the IPM loop.  After the factor kernel of every iteration the host reads the
@@ -1759,23 +1756,23 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         {
             /* the last survivors of a one-instance-per-lane level: a wave that still has ONE active lane pays
              * the full per-wave latency of every sweep, so the tail continues one wave per instance */
-            compact_into(b, root, nact, s, true);
+            ocp_qp_gpu_batch *tail = compact_into(b, root, s, SUB_TAIL);
             root->n_tail_switches++;
-            run_ipm(b->tail, root, prof, s, it);
+            run_ipm(tail, root, prof, s, it);
             /* the family's own finalize first: the general one-instance-per-lane kernels refresh the multipliers
              * of the fixed variables in every factor sweep and their finalize relies on that, the wave-per-instance
              * kernels compute them once at the end */
-            GQP_IPM_LAUNCH(b->tail, pick_kernels(b->tail).final_, s, b->tail->D);
+            GQP_IPM_LAUNCH(tail, pick_kernels(tail).final_, s, tail->D);
             root->launches++;
-            compact_back(b, s, b->tail, it);
+            compact_back(b, s, SUB_TAIL, it);
             break;
         }
         if (b->B >= root->compact_min && 2 * nact <= b->B)
         {
-            compact_into(b, root, nact, s, false);
+            ocp_qp_gpu_batch *level = compact_into(b, root, s, SUB_COMPACT);
             root->n_compactions++;
-            run_ipm(b->compact, root, prof, s, it);
-            compact_back(b, s, b->compact, it);
+            run_ipm(level, root, prof, s, it);
+            compact_back(b, s, SUB_COMPACT, it);
             break;
         }
         if (b == root) prof.begin(2, s);
@@ -1882,12 +1879,115 @@ static void polish_pass(ocp_qp_gpu_batch *b, Prof &prof, hipStream_t s)
     }
 }
 
+/* Sub-batches (SubRole): creation, option hand-down, load and store exist once, here.  What differs per role stays with the callers:
+ * how the list is built, n_active and the statistics rows of the levels, the order inside a sensitivity slice, the scalars a
+ * ric_alg 0 solve reports */
+typedef GArr GqpDev::*GqpArrMember;
 /* arrays that define a QP instance and its iterate (everything else is recomputed) */
-#define GQP_FOR_STATE_ARRAYS(X) X(BAt) X(bvec) X(RSQ) X(rq) X(dvec) X(DCt) X(Zz) X(ux) X(sv) X(pi) X(lam) X(t)
-#define GQP_FOR_RESULT_ARRAYS(X) X(ux) X(sv) X(pi) X(lam) X(t)
+static const std::vector<GqpArrMember> g_state_arrays = {&GqpDev::BAt, &GqpDev::bvec, &GqpDev::RSQ, &GqpDev::rq, &GqpDev::dvec, &GqpDev::DCt,
+                                                         &GqpDev::Zz, &GqpDev::ux, &GqpDev::sv, &GqpDev::pi, &GqpDev::lam, &GqpDev::t};
+/* what comes back: the iterate of a solve, the directions of a seed pass, the factor at the solution */
+static const std::vector<GqpArrMember> g_result_arrays = {&GqpDev::ux, &GqpDev::sv, &GqpDev::pi, &GqpDev::lam, &GqpDev::t};
+static const std::vector<GqpArrMember> g_direction_arrays = {&GqpDev::dux, &GqpDev::dsv, &GqpDev::dpi, &GqpDev::dlam, &GqpDev::dt};
+static const std::vector<GqpArrMember> g_factor_arrays = {&GqpDev::Lf, &GqpDev::lf};
+enum SubStore { SUB_RESULT, SUB_DIRECTION, SUB_FACTOR };
 
-static void compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, int nact, hipStream_t s, bool tail)
+/* room for n entries in the device list of a role */
+static void sub_list_reserve(ocp_qp_gpu_batch *b, SubBatch &sb, int n)
 {
+    if (sb.d_list && n <= sb.list_cap) return;
+    sb.list_cap = n;
+    sb.d_list = dalloc<int>(b, n);
+}
+
+/* the sub-batch of `role` for `cap` instances of b: the very kernel set of b (compaction) or the wave-per-instance family at the very
+ * same padded dims (every other role).  Not being able to make one is a device failure like any other: the entry returns -1 */
+static ocp_qp_gpu_batch *sub_batch_create(ocp_qp_gpu_batch *b, SubRole role, int cap)
+{
+    static const char *const names[SUB_ROLES] = {"compaction", "tail", "classical-Riccati", "sensitivity"};
+    const bool wpi = role != SUB_COMPACT;
+    ocp_qp_gpu_batch *c = batch_create_shape(b->N, b->nx.data(), b->nu.data(), b->nbx.data(), b->nbu.data(), b->ng.data(), b->ns.data(), cap,
+                                             b->device, wpi ? b->ks->NX : 0, wpi ? b->ks->NU : 0, b->ks, wpi);
+    if (!c)
+    {
+        fprintf(stderr, "acados_amd: cannot create the %s sub-batch\n", names[role]);
+        throw gqp_hip_failure{-1};
+    }
+    if (b->stream_priority) set_stream_priority(c, b->stream_priority);
+    c->idxb = b->idxb; c->idxs_rev = b->idxs_rev; c->idxe = b->idxe; c->nbxe = b->nbxe;
+    switch (role)
+    {
+    case SUB_COMPACT: /* the family of the parent goes with its kernel set */
+        c->aos = b->aos; c->wpi = b->wpi; c->shmem = b->shmem; c->shmem_fwd = b->shmem_fwd; c->shmem_fact = b->shmem_fact;
+        c->w16 = b->w16; c->w16_soft = b->w16_soft; c->w16_ng = b->w16_ng; c->w16_shmem = b->w16_shmem;
+        c->w16_shmem_fact = b->w16_shmem_fact; c->w16_tiles = b->w16_tiles;
+        /* fall through */
+    case SUB_TAIL: /* a level sizes the sub-batches below it by the thresholds it was made under */
+        c->compact_min = b->compact_min; c->tail_max = b->tail_max; c->tail_div = b->tail_div;
+        break;
+    case SUB_RIC0:
+        c->ric_alg = 0;
+        ric_configure(c);
+        break;
+    case SUB_SENS:
+        c->tail_max = 0;
+        c->ric_alg = b->ric_alg; /* the factor at the solution in the layout of the batch's Riccati recursion */
+        ric_configure(c);
+        break;
+    default: break;
+    }
+    finalize_structure(c);
+    if (role == SUB_SENS) c->sfix = garr<double>(c, (size_t) (c->N + 2) * (c->D.NX + c->D.NU));
+    b->sub[role].c = c;
+    b->sub[role].cap = cap;
+    return c;
+}
+
+/* Run options of the solving batch for a sub-batch: per role what is handed down, no more */
+static void sub_batch_opts(const ocp_qp_gpu_batch *from, ocp_qp_gpu_batch *c, SubRole role)
+{
+    /* every role: the IPM options and the exit scale of the soft classes (effective_opts).  For the two levels `from` is the ROOT of
+     * the solve, not the level above.  The sensitivity sub-batch only factorises and sweeps: it needs nothing else */
+    c->O = from->O;
+    c->tol_comp_soft_scale = from->tol_comp_soft_scale;
+    if (role != SUB_RIC0) return;
+    /* the classical-Riccati sub-batch runs a whole solve of its own: polish pass, printing, profiling, the compaction and
+     * single-launch thresholds, the hot-start clips (a wave-per-instance batch has no tail and holds no dynamics: not those) */
+    c->polish = from->polish; c->polish_ratio = from->polish_ratio; c->polish_min = from->polish_min;
+    c->print_level = from->print_level; c->profile = from->profile; c->compact_min = from->compact_min; c->solve_max = from->solve_max;
+    c->t0_min = from->t0_min; c->lam0_min = from->lam0_min;
+}
+
+static void sub_copy(ocp_qp_gpu_batch *b, const SubBatch &sb, const std::vector<GqpArrMember> &arrays, int cnt, int dir, hipStream_t s)
+{
+    for (GqpArrMember m : arrays) copy_level(b->D.*m, sb.c->D.*m, sb.d_list, cnt, dir, s);
+}
+
+/* QP data, iterate, activity masks and loop scalars of the `cnt` listed instances of b into the first slots of the sub-batch.
+ * Returns with the copies done: the caller may reuse its host list, the sub-batch may launch on a stream of its own */
+static void sub_batch_load(ocp_qp_gpu_batch *b, const SubBatch &sb, int cnt, hipStream_t s)
+{
+    ocp_qp_gpu_batch *c = sb.c;
+    c->B = cnt; /* the sub-batch works on `cnt` slots of its capacity */
+    c->D.B = cnt;
+    sub_copy(b, sb, g_state_arrays, cnt, 0, s);
+    copy_level(b->D.amask, c->D.amask, sb.d_list, cnt, 0, s);
+    hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), dim3(64), 0, s, b->D, c->D, sb.d_list, cnt, 0);
+    HIPCHK(hipStreamSynchronize(s));
+}
+
+/* ... and back: the iterate with the per-instance scalars of a solve, the directions of a seed pass, or the factor (not synchronised) */
+static void sub_batch_store(ocp_qp_gpu_batch *b, const SubBatch &sb, int cnt, SubStore what, hipStream_t s)
+{
+    sub_copy(b, sb, what == SUB_RESULT ? g_result_arrays : what == SUB_DIRECTION ? g_direction_arrays : g_factor_arrays, cnt, 1, s);
+    if (what == SUB_RESULT)
+        hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), dim3(64), 0, s, b->D, sb.c->D, sb.d_list, cnt, 1);
+}
+
+static ocp_qp_gpu_batch *compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, hipStream_t s, SubRole role)
+{
+    const bool tail = role == SUB_TAIL;
+    SubBatch &sb = b->sub[role];
     /* sorted list of the still-iterating instances (sorted => the gather reads stay coalesced) */
     int *st = b->h_ints, *list = b->h_ints + b->Bp; /* pinned, owned by the level */
     HIPCHK(hipMemcpy(st, b->D.status, sizeof(int) * b->B, hipMemcpyDeviceToHost));
@@ -1895,67 +1995,47 @@ static void compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, int nact, 
     for (int i = 0; i < b->B; i++) if (st[i] == GQP_RUNNING) list[cnt++] = i;
     /* capacities follow the level's CAPACITY (Bp), not its current count: a level is re-used by later solves with
      * more survivors (its B changes between solves) */
-    if (!b->d_list || cnt > b->list_cap)
-    {
-        b->list_cap = std::max(cnt, (b->Bp + 1) / 2);
-        b->d_list = dalloc<int>(b, b->list_cap);
-    }
-    ocp_qp_gpu_batch *&slot = tail ? b->tail : b->compact;
-    if (slot && cnt > (tail ? b->tail_cap : slot->Bp))
+    sub_list_reserve(b, sb, std::max(cnt, (b->Bp + 1) / 2));
+    if (sb.c && cnt > (tail ? sb.cap : sb.c->Bp))
     {
         /* more survivors than the sub-batch was sized for (tail_max raised, or a later solve of a re-used level) */
-        ocp_qp_gpu_batch_destroy(slot);
-        slot = nullptr;
+        ocp_qp_gpu_batch_destroy(sb.c);
+        sb.c = nullptr;
     }
-    if (!slot)
-    {
-        /* same kernel set (compaction) or the wave-per-instance family at the very same padded dims (tail) */
-        const int cap = tail ? std::max(cnt, std::min(b->tail_max, b->list_cap)) : std::max(cnt, (b->Bp + 1) / 2);
-        if (tail) b->tail_cap = cap;
-        ocp_qp_gpu_batch *c = batch_create_shape(b->N, b->nx.data(), b->nu.data(), b->nbx.data(), b->nbu.data(),
-                                                 b->ng.data(), b->ns.data(), cap, b->device, tail ? b->ks->NX : 0, tail ? b->ks->NU : 0,
-                                                 b->ks, tail);
-        if (c && b->stream_priority) set_stream_priority(c, b->stream_priority);
-        if (!c) { fprintf(stderr, "acados_amd: cannot create the compaction sub-batch\n"); exit(1); }
-        c->idxb = b->idxb; c->idxs_rev = b->idxs_rev; c->idxe = b->idxe; c->nbxe = b->nbxe;
-        c->compact_min = b->compact_min;
-        c->tail_max = b->tail_max;
-        c->tail_div = b->tail_div;
-        if (!tail) { c->aos = b->aos; c->wpi = b->wpi; c->shmem = b->shmem; c->shmem_fwd = b->shmem_fwd; c->shmem_fact = b->shmem_fact; c->w16 = b->w16; c->w16_soft = b->w16_soft; c->w16_ng = b->w16_ng; c->w16_shmem = b->w16_shmem; c->w16_shmem_fact = b->w16_shmem_fact; c->w16_tiles = b->w16_tiles; }
-        finalize_structure(c);
-        slot = c;
-    }
-    ocp_qp_gpu_batch *c = slot;
-    HIPCHK(hipMemcpyAsync(b->d_list, list, sizeof(int) * cnt, hipMemcpyHostToDevice, s));
-    c->B = cnt; /* the level works on `cnt` slots of its capacity */
-    c->D.B = cnt;
-    const dim3 block(64);
-#define GQP_COPY_IN(A) copy_level(b->D.A, c->D.A, b->d_list, cnt, 0, s);
-    GQP_FOR_STATE_ARRAYS(GQP_COPY_IN)
-#undef GQP_COPY_IN
-    copy_level(b->D.amask, c->D.amask, b->d_list, cnt, 0, s);
-    hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), block, 0, s, b->D, c->D, b->d_list, cnt, 0);
+    if (!sb.c) sub_batch_create(b, role, tail ? std::max(cnt, std::min(b->tail_max, sb.list_cap)) : std::max(cnt, (b->Bp + 1) / 2));
+    ocp_qp_gpu_batch *c = sb.c;
+    HIPCHK(hipMemcpyAsync(sb.d_list, list, sizeof(int) * cnt, hipMemcpyHostToDevice, s));
+    sub_batch_load(b, sb, cnt, s); /* (synchronises: `list` (host) must outlive the copy) */
     *c->h_nact = cnt;
     HIPCHK(hipMemcpyAsync(c->D.n_active, c->h_nact, sizeof(int), hipMemcpyHostToDevice, s));
     /* the level keeps its own statistics rows for its first slots; merged into the parent's table afterwards */
-    c->O = root->O;
-    c->tol_comp_soft_scale = root->tol_comp_soft_scale;
+    sub_batch_opts(root, c, role);
     ensure_stat(c);
     HIPCHK(hipMemsetAsync(c->D.stat, 0, sizeof(double) * (size_t) c->stat_rows * GQP_STAT_COLS * c->stat_inst, s));
-    HIPCHK(hipStreamSynchronize(s)); /* `list` (host) must outlive the copy */
+    return c;
 }
 
-static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, ocp_qp_gpu_batch *c, int it0)
+static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, SubRole role, int it0)
 {
+    const SubBatch &sb = b->sub[role];
+    ocp_qp_gpu_batch *c = sb.c;
     const int cnt = c->B;
     if (b->D.stat && c->D.stat)
         hipLaunchKernelGGL(gqp::k_stat_merge, dim3(1, std::max(1, std::min(b->stat_rows, c->stat_rows) - it0)), dim3(64), 0, s, b->D,
-                           c->D, b->d_list, cnt < 64 ? cnt : 64, it0);
-    const dim3 block(64);
-#define GQP_COPY_OUT(A) copy_level(b->D.A, c->D.A, b->d_list, cnt, 1, s);
-    GQP_FOR_RESULT_ARRAYS(GQP_COPY_OUT)
-#undef GQP_COPY_OUT
-    hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), block, 0, s, b->D, c->D, b->d_list, cnt, 1);
+                           c->D, sb.d_list, cnt < 64 ? cnt : 64, it0);
+    sub_batch_store(b, sb, cnt, SUB_RESULT, s);
+}
+
+/* behind a solve: iteration counts and statuses into h_ints; sets last_iters, returns the number of instances that failed */
+static int solve_epilogue(ocp_qp_gpu_batch *b)
+{
+    int *itv = b->h_ints, *st = b->h_ints + b->Bp;
+    HIPCHK(hipMemcpy(itv, b->D.iter, sizeof(int) * b->B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st, b->D.status, sizeof(int) * b->B, hipMemcpyDeviceToHost));
+    int mx = 0, bad = 0;
+    for (int q = 0; q < b->B; q++) { mx = std::max(mx, itv[q]); bad += st[q] != 0; }
+    b->last_iters = mx;
+    return bad;
 }
 
 /*
@@ -2029,65 +2109,37 @@ static int dense_solve(ocp_qp_gpu_batch *b)
     b->time_xcond = 0.0;
     b->factor_stale = true;   /* Lf of the stage-wise sweeps does not belong to this solution: the sensitivity slots refactor */
     b->sens_open = false;
-    int *itv = b->h_ints, *st = b->h_ints + b->Bp;
-    HIPCHK(hipMemcpy(itv, D.iter, sizeof(int) * b->B, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(st, D.status, sizeof(int) * b->B, hipMemcpyDeviceToHost));
-    int mx = 0, bad = 0;
-    for (int q = 0; q < b->B; q++) { mx = std::max(mx, itv[q]); bad += st[q] != 0; }
-    b->last_iters = mx;
-    return bad;
+    return solve_epilogue(b);
 }
 
 static void refactor_at_solution(ocp_qp_gpu_batch *b);
 
 /*
  * ric_alg 0 on a one-instance-per-lane batch: the classical sweeps exist in the wave-per-instance family only.  The whole
- * batch (QP data, iterate, loop scalars) is copied into ric0_child -- that family at the same padded dims, the conversion of
+ * batch (QP data, iterate, loop scalars) is copied into sub[SUB_RIC0] -- that family at the same padded dims, the conversion of
  * the tail switch --, solved there, and the iterate, the factor at the solution and the per-instance results come back.
  */
 static ocp_qp_gpu_batch *ric0_copy_in(ocp_qp_gpu_batch *b)
 {
-    hipStream_t s = b->stream;
-    if (!b->ric0_child)
+    SubBatch &sb = b->sub[SUB_RIC0];
+    if (!sb.c)
     {
-        ocp_qp_gpu_batch *c = batch_create_shape(b->N, b->nx.data(), b->nu.data(), b->nbx.data(), b->nbu.data(), b->ng.data(),
-                                                 b->ns.data(), b->B, b->device, b->ks->NX, b->ks->NU, b->ks, true);
-        if (!c) { fprintf(stderr, "acados_amd: cannot create the classical-Riccati sub-batch\n"); return nullptr; }
-        if (b->stream_priority) set_stream_priority(c, b->stream_priority);
-        c->idxb = b->idxb; c->idxs_rev = b->idxs_rev; c->idxe = b->idxe; c->nbxe = b->nbxe;
-        c->ric_alg = 0;
-        ric_configure(c);
-        finalize_structure(c);
-        std::vector<int> list(b->B);
+        sub_batch_create(b, SUB_RIC0, b->B);
+        std::vector<int> list(b->B); /* 0 .. B-1: the whole batch goes */
         for (int i = 0; i < b->B; i++) list[i] = i;
-        if (!b->d_rlist) b->d_rlist = dalloc<int>(b, b->Bp);
-        HIPCHK(hipMemcpy(b->d_rlist, list.data(), sizeof(int) * b->B, hipMemcpyHostToDevice));
-        b->ric0_child = c;
+        sub_list_reserve(b, sb, b->Bp);
+        HIPCHK(hipMemcpy(sb.d_list, list.data(), sizeof(int) * b->B, hipMemcpyHostToDevice));
     }
-    ocp_qp_gpu_batch *c = b->ric0_child;
-    c->O = b->O;
-    c->tol_comp_soft_scale = b->tol_comp_soft_scale;
-    c->polish = b->polish; c->polish_ratio = b->polish_ratio; c->polish_min = b->polish_min;
-    c->print_level = b->print_level; c->profile = b->profile; c->compact_min = b->compact_min; c->solve_max = b->solve_max;
-    c->t0_min = b->t0_min; c->lam0_min = b->lam0_min;
-    const int cnt = b->B;
-    const dim3 block(64);
-#define GQP_COPY_IN(A) copy_level(b->D.A, c->D.A, b->d_rlist, cnt, 0, s);
-    GQP_FOR_STATE_ARRAYS(GQP_COPY_IN)
-#undef GQP_COPY_IN
-    copy_level(b->D.amask, c->D.amask, b->d_rlist, cnt, 0, s);
-    hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), block, 0, s, b->D, c->D, b->d_rlist, cnt, 0);
-    HIPCHK(hipStreamSynchronize(s)); /* the sub-batch works on its own stream */
-    return c;
+    sub_batch_opts(b, sb.c, SUB_RIC0);
+    sub_batch_load(b, sb, b->B, b->stream); /* (synchronises: the sub-batch works on its own stream) */
+    return sb.c;
 }
 
-/* the factor of ric0_child (classical layout) into the parent's Lf / lf */
-static void ric0_factor_back(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *c)
+/* the factor of the classical-Riccati sub-batch (classical layout) into the parent's Lf / lf */
+static void ric0_factor_back(ocp_qp_gpu_batch *b)
 {
-    hipStream_t s = b->stream;
-    copy_level(b->D.Lf, c->D.Lf, b->d_rlist, b->B, 1, s);
-    copy_level(b->D.lf, c->D.lf, b->d_rlist, b->B, 1, s);
-    HIPCHK(hipStreamSynchronize(s));
+    sub_batch_store(b, b->sub[SUB_RIC0], b->B, SUB_FACTOR, b->stream);
+    HIPCHK(hipStreamSynchronize(b->stream));
     b->factor_stale = false;
 }
 
@@ -2095,27 +2147,18 @@ static void ric0_factor_back(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *c)
  * square-root layout, which the getters would read as the classical one */
 static void ric0_refactor(ocp_qp_gpu_batch *b)
 {
-    ocp_qp_gpu_batch *c = ric0_copy_in(b);
-    if (!c) throw gqp_hip_failure{-1};
-    refactor_at_solution(c);
-    ric0_factor_back(b, c);
+    refactor_at_solution(ric0_copy_in(b));
+    ric0_factor_back(b);
 }
 
 static int ric0_solve(ocp_qp_gpu_batch *b)
 {
-    hipStream_t s = b->stream;
     ocp_qp_gpu_batch *c = ric0_copy_in(b);
-    if (!c) return -1;
-    const int cnt = b->B;
-    const dim3 block(64);
     const int bad = ocp_qp_gpu_batch_solve(c);
     if (bad < 0) return bad;
     if (c->factor_stale) refactor_at_solution(c);
-#define GQP_COPY_OUT(A) copy_level(b->D.A, c->D.A, b->d_rlist, cnt, 1, s);
-    GQP_FOR_RESULT_ARRAYS(GQP_COPY_OUT)
-#undef GQP_COPY_OUT
-    hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), block, 0, s, b->D, c->D, b->d_rlist, cnt, 1);
-    ric0_factor_back(b, c);
+    sub_batch_store(b, b->sub[SUB_RIC0], b->B, SUB_RESULT, b->stream);
+    ric0_factor_back(b);
     b->time_tot = c->time_tot; b->time_xcond = 0.0;
     b->last_iters = c->last_iters; b->launches = c->launches;
     b->n_compactions = c->n_compactions; b->n_tail_switches = 0; b->n_single_launch = c->n_single_launch;
@@ -2184,13 +2227,6 @@ try
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
     b->time_tot = ms * 1e-3;
-    {
-        int *itv = b->h_ints;
-        HIPCHK(hipMemcpy(itv, D.iter, sizeof(int) * b->B, hipMemcpyDeviceToHost));
-        int mx = 0;
-        for (int q = 0; q < b->B; q++) mx = std::max(mx, itv[q]);
-        b->last_iters = mx;
-    }
     for (size_t q = 0; q < b->prof_cls.size(); q++)
     {
         float pm = 0.f;
@@ -2198,12 +2234,7 @@ try
         b->prof_ms[b->prof_cls[q]] += pm;
         b->prof_cnt[b->prof_cls[q]]++;
     }
-
-    int *st = b->h_ints + b->Bp;
-    HIPCHK(hipMemcpy(st, D.status, sizeof(int) * b->B, hipMemcpyDeviceToHost));
-    int bad = 0;
-    for (int i = 0; i < b->B; i++) bad += st[i] != 0;
-    return bad;
+    return solve_epilogue(b);
 }
 catch (const gqp_hip_failure &) { return -1; }
 
@@ -2326,54 +2357,30 @@ static void sens_pass(ocp_qp_gpu_batch *b, hipStream_t s)
 static void sens_solve_sliced(ocp_qp_gpu_batch *b)
 {
     hipStream_t s = b->stream;
-    const char *env = getenv("ACADOS_AMD_SENS_SLICE");
-    const int cap = b->sens_child ? b->sens_cap : std::min(b->B, env && atoi(env) > 0 ? atoi(env) : GQP_SENS_SLICE);
-    if (!b->sens_child)
+    SubBatch &sb = b->sub[SUB_SENS];
+    if (!sb.c)
     {
-        ocp_qp_gpu_batch *c = batch_create_shape(b->N, b->nx.data(), b->nu.data(), b->nbx.data(), b->nbu.data(), b->ng.data(),
-                                                 b->ns.data(), cap, b->device, b->ks->NX, b->ks->NU, b->ks, true);
-        if (c && b->stream_priority) set_stream_priority(c, b->stream_priority);
-        if (!c) { fprintf(stderr, "acados_amd: cannot create the sensitivity sub-batch\n"); exit(1); }
-        c->idxb = b->idxb; c->idxs_rev = b->idxs_rev; c->idxe = b->idxe; c->nbxe = b->nbxe;
-        c->tail_max = 0;
-        c->ric_alg = b->ric_alg; /* the factor at the solution in the layout of the batch's Riccati recursion */
-        ric_configure(c);
-        finalize_structure(c);
-        const int n = c->D.NX + c->D.NU;
-        c->sfix = garr<double>(c, (size_t) (c->N + 2) * n);
-        b->sens_child = c;
-        b->sens_cap = cap;
-        b->d_slist = dalloc<int>(b, cap);
+        const char *env = getenv("ACADOS_AMD_SENS_SLICE"); /* the slice size is fixed at first use */
+        sub_batch_create(b, SUB_SENS, std::min(b->B, env && atoi(env) > 0 ? atoi(env) : GQP_SENS_SLICE));
+        sub_list_reserve(b, sb, sb.cap);
     }
-    ocp_qp_gpu_batch *c = b->sens_child;
-    c->O = b->O;
-    c->tol_comp_soft_scale = b->tol_comp_soft_scale;
+    ocp_qp_gpu_batch *c = sb.c;
+    const int cap = sb.cap;
+    sub_batch_opts(b, c, SUB_SENS);
     std::vector<int> list(cap);
-    const dim3 block(64);
     for (int i0 = 0; i0 < b->B; i0 += cap)
     {
         const int cnt = std::min(cap, b->B - i0);
         for (int j = 0; j < cnt; j++) list[j] = i0 + j;
-        HIPCHK(hipMemcpyAsync(b->d_slist, list.data(), sizeof(int) * cnt, hipMemcpyHostToDevice, s));
-        c->B = cnt;
-        c->D.B = cnt;
-#define GQP_SLICE_COPY(SRC, DST, DIR) copy_level(SRC, DST, b->d_slist, cnt, DIR, s);
-#define GQP_COPY_IN(A) GQP_SLICE_COPY(b->D.A, c->D.A, 0)
-        GQP_FOR_STATE_ARRAYS(GQP_COPY_IN)
-        copy_level(b->D.amask, c->D.amask, b->d_slist, cnt, 0, s);
-        hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), block, 0, s, b->D, c->D, b->d_slist, cnt, 0);
-        HIPCHK(hipStreamSynchronize(s)); /* the sub-batch works on its own stream */
-        refactor_at_solution(c);         /* writes the residual arrays: the seeds go in afterwards */
-        GQP_COPY_IN(rg) GQP_COPY_IN(rgs) GQP_COPY_IN(rb) GQP_COPY_IN(rd)
-#undef GQP_COPY_IN
-        GQP_SLICE_COPY(b->sfix, c->sfix, 0)
+        HIPCHK(hipMemcpyAsync(sb.d_list, list.data(), sizeof(int) * cnt, hipMemcpyHostToDevice, s));
+        sub_batch_load(b, sb, cnt, s); /* (synchronises: the sub-batch works on its own stream) */
+        refactor_at_solution(c);       /* writes the residual arrays: the seeds go in afterwards */
+        for (GqpArrMember m : {&GqpDev::rg, &GqpDev::rgs, &GqpDev::rb, &GqpDev::rd}) copy_level(b->D.*m, c->D.*m, sb.d_list, cnt, 0, s);
+        copy_level(b->sfix, c->sfix, sb.d_list, cnt, 0, s);
         HIPCHK(hipStreamSynchronize(s));
         sens_pass(c, c->stream);
         HIPCHK(hipStreamSynchronize(c->stream));
-#define GQP_COPY_OUT(A) GQP_SLICE_COPY(b->D.A, c->D.A, 1)
-        GQP_COPY_OUT(dux) GQP_COPY_OUT(dsv) GQP_COPY_OUT(dpi) GQP_COPY_OUT(dlam) GQP_COPY_OUT(dt)
-#undef GQP_COPY_OUT
-#undef GQP_SLICE_COPY
+        sub_batch_store(b, sb, cnt, SUB_DIRECTION, s);
         HIPCHK(hipStreamSynchronize(s));
     }
 }
@@ -2561,7 +2568,7 @@ try
 {
     HIPCHK(hipSetDevice(b->device));
     if (b->pcond_state == 1 && b->child) return ocp_qp_gpu_batch_get_stat(b->child, inst, stat, max_rows);
-    if (b->ric_alg == 0 && !b->wpi && b->ric0_child) return ocp_qp_gpu_batch_get_stat(b->ric0_child, inst, stat, max_rows);
+    if (b->ric_alg == 0 && !b->wpi && b->sub[SUB_RIC0].c) return ocp_qp_gpu_batch_get_stat(b->sub[SUB_RIC0].c, inst, stat, max_rows);
     if (!b->D.stat || inst < 0 || inst >= b->stat_inst) return -1;
     const int rows = std::min(max_rows, b->stat_rows);
     std::vector<double> h((size_t) b->stat_rows * GQP_STAT_COLS * b->stat_inst);
