@@ -243,6 +243,7 @@ struct ocp_qp_gpu_batch
     /* held dynamics of the one-instance-per-lane box sweeps (ipm_kernels_box.hpp; run_ipm) */
     int hold_dynamics = 1;               /* option: 1 = tiles whose [B A]' is found stage-invariant keep it in registers, 0 = never */
     int n_tiles_invariant = 0;           /* tiles found so by the last solve */
+    int n_rhs_held_launches = 0;         /* launches of the held rhs entry (IpmKernels::rhs_held) in the last solve */
     /* solution sensitivities / factor at the solution */
     bool factor_stale = false;           /* the last solve finished instances on a sub-level: Lf of the root is not theirs */
     bool sens_open = false;              /* seeds are being collected (rg, rb, rd hold seeds, not residuals) */
@@ -1569,6 +1570,7 @@ static int pcond_solve(ocp_qp_gpu_batch *b, int mode = 3)
 struct IpmKernels
 {
     kern_redo_t fact, rhs, faff, fcorr;
+    kern_redo_t rhs_held; /* K.rhs with [B A]' held across the stages, for a launch whose tiles are all held; null: there is none */
     kern_plain_t final_;
 };
 
@@ -1603,9 +1605,11 @@ static IpmKernels pick_kernels(const ocp_qp_gpu_batch *b)
     k.rhs = b->use_box ? ks->box_rhs[xb] : ks->back_rhs;
     k.faff = b->use_box ? ks->box_fwd_aff[xb] : ks->fwd_aff;
     k.fcorr = b->use_box ? ks->box_fwd_corr[xb] : ks->fwd_corr;
+    k.rhs_held = (b->use_box && !b->wpi && !xb) ? ks->box_rhs_held : nullptr;
     if (b->use_box && !b->wpi && b->kb_plain && ks->kb_fact[xb])
     {
         k.fact = ks->kb_fact[xb]; k.rhs = ks->kb_rhs[xb]; k.faff = ks->kb_fwd_aff[xb]; k.fcorr = ks->kb_fwd_corr[xb];
+        k.rhs_held = xb ? nullptr : ks->kb_rhs_held;
     }
     k.final_ = b->use_box ? ks->box_finalize : ks->finalize;
     return k;
@@ -1650,7 +1654,10 @@ static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, SubRole role, int i
  * Held dynamics (ipm_kernels_box.hpp): the ROOT level zeroes GqpDev::tile_inv in front of its loop and behind it, lets its first
  * affine forward sweep count the lanes with stage-invariant [B A]' into it (GqpOpts::hold bit 1) and runs every sweep of its loop
  * with GqpOpts::hold bit 0.  The counters are read back behind that sweep and counted at the loop's next synchronisation
- * ("tiles_invariant").  Sub-levels never set either bit and their counters stay zero: nothing is copied by compact_into.  Every
+ * ("tiles_invariant").  From then on, if EVERY tile of the batch is held, both rhs-only launches of an iteration go to the entry
+ * that holds the block too (IpmKernels::rhs_held, gqp::kh_backrhs; counted in "rhs_held_launches"); a mixed batch, the iteration that
+ * detects and every launch outside this loop (sub-levels, tail, sensitivities, ric_alg 0) keep K.rhs, which fetches at every
+ * stage.  Sub-levels never set either bit and their counters stay zero: nothing is copied by compact_into.  Every
  * other launch of these kernels (sensitivities, a later solve, the polish pass -- a root loop of its own, which detects again)
  * finds the counters at zero.
  */
@@ -1678,6 +1685,13 @@ static const int *side_map(ocp_qp_gpu_batch *b)
     return b->d_side_map;
 }
 
+/* 1: the host waits for the detector's counters right behind the detecting sweep, so that the rhs pair of that iteration is held
+ * too -- one held launch pair more per solve for one drained queue (the cross-check: make variant TAG=holdsync
+ * DEFS=-DGQP_HOLD_SYNC=1, tools/variant_rate.py c2 libacados_amd_qp_holdsync.so; kept at 0 until both are measured, profiles/NOTES.md) */
+#ifndef GQP_HOLD_SYNC
+#define GQP_HOLD_SYNC 0
+#endif
+
 static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hipStream_t s, int it)
 {
     const IpmKernels K = pick_kernels(b);
@@ -1698,6 +1712,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
     if (b == root)
     {
         root->n_tiles_invariant = 0;
+        root->n_rhs_held_launches = 0;
         HIPCHK(hipMemsetAsync(D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
     }
     GqpOpts Oc = O; /* options of the corrector-sweep launches */
@@ -1725,6 +1740,12 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         }
         /* (never taken: a row leaves the kernel only with its instance out of the RUNNING state) */
     }
+    const auto count_tiles = [&]() {
+        int full = 0;
+        for (int q = 0; q < (b->B + 63) / 64; q++) full += b->h_ints[q] == std::min(64, b->B - 64 * q);
+        root->n_tiles_invariant = full;
+        counted = true;
+    };
     for (;; it++)
     {
         if (b == root) prof.begin(1, s); /* per-class timing covers the root level only (full-batch launches) */
@@ -1734,13 +1755,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         const int nact = *b->h_nact;
-        if (!detect && !counted)
-        {
-            int full = 0;
-            for (int q = 0; q < (b->B + 63) / 64; q++) full += b->h_ints[q] == std::min(64, b->B - 64 * q);
-            root->n_tiles_invariant = full;
-            counted = true;
-        }
+        if (!detect && !counted) count_tiles();
         if (root->print_level > 1) printf("acados_amd: ipm iter %d level size %d active %d\n", it, b->B, nact);
         if (nact <= 0 || it > O.iter_max) break;
         if (use_perm && nact >= 1 && 6 * nact <= 5 * b->w16_slots)
@@ -1786,9 +1801,18 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         {
             HIPCHK(hipMemcpyAsync(b->h_ints, D.tile_inv, sizeof(int) * (size_t) (b->Bp / 64), hipMemcpyDeviceToHost, s));
             detect = false;
+#if GQP_HOLD_SYNC
+            HIPCHK(hipStreamSynchronize(s));
+            count_tiles();
+#endif
         }
+        /* the rhs pair of this iteration: the held entry when EVERY tile of the root batch was found stage-invariant -- it reads no
+         * flag, so one tile that must fetch keeps K.rhs for the whole launch, and so does the iteration whose counters have not
+         * arrived yet (the one that detects) */
+        const bool rhs_held = hold && K.rhs_held && counted && root->n_tiles_invariant == (b->B + 63) / 64;
+        const kern_redo_t k_rhs = rhs_held ? K.rhs_held : K.rhs;
         if (b == root) prof.begin(3, s);
-        GQP_SWEEP_LAUNCH(b, K.rhs, b->shmem, s, D, O, 0);
+        GQP_SWEEP_LAUNCH(b, k_rhs, b->shmem, s, D, O, 0);
         if (b == root) prof.end(s);
         if (b == root) prof.begin(4, s);
         GQP_SWEEP_LAUNCH(b, K.fcorr, b->shmem_fwd, s, D, Oc, 0);
@@ -1796,10 +1820,11 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         root->launches += 3;
         if (O.cond_pred_corr)
         {
-            GQP_SWEEP_LAUNCH(b, K.rhs, b->shmem, s, D, O, 1);
+            GQP_SWEEP_LAUNCH(b, k_rhs, b->shmem, s, D, O, 1);
             GQP_SWEEP_LAUNCH(b, K.fcorr, b->shmem_fwd, s, D, Oc, 1);
             root->launches += 2;
         }
+        if (rhs_held) root->n_rhs_held_launches += O.cond_pred_corr ? 2 : 1;
         if (ext_update)
         {
             /* (behind the redo pair: an instance whose corrector collapsed gets its step length there) */
@@ -1860,8 +1885,10 @@ static void polish_pass(ocp_qp_gpu_batch *b, Prof &prof, hipStream_t s)
     b->O.tau_min = Oeff.tau_min; /* the barrier floor of the solve (derived from ITS tol_comp) */
     D.stat_inst = 0;             /* the statistics table keeps the solve's rows */
     const int keep_inv = b->n_tiles_invariant; /* ("tiles_invariant" speaks of the solve) */
+    const int keep_held = b->n_rhs_held_launches;
     run_ipm(b, b, prof, s, 0);
     b->n_tiles_invariant = keep_inv;
+    b->n_rhs_held_launches += keep_held; /* ("rhs_held_launches": every launch of the held entry, this pass's included) */
     b->O = keep;
     D.stat_inst = keep_stat;
     hipLaunchKernelGGL(gqp::k_polish_restore, g64, blk, 0, s, D, Oeff, b->d_pol_status, b->d_pol_iter, b->d_pol_sc, b->d_pol_flag, b->d_pol_cnt + 1);
@@ -2592,6 +2619,7 @@ try
     if (!strcmp(f, "w16_tiles")) return (double) b->w16_tiles;
     if (!strcmp(f, "tail_switches")) return (double) b->n_tail_switches;
     if (!strcmp(f, "tiles_invariant")) return (double) b->n_tiles_invariant;
+    if (!strcmp(f, "rhs_held_launches")) return (double) b->n_rhs_held_launches;
     if (!strcmp(f, "single_launch_solves")) return (double) b->n_single_launch;
     if (!strcmp(f, "cond_N_active")) return b->pcond_state == 1 ? (double) b->child->N : (double) b->N;
     if (!strcmp(f, "tol_comp_soft_scale")) return b->tol_comp_soft_scale;

@@ -17,7 +17,8 @@
  *     Mehrotra corrector needs) and neither dux nor dpi; mu_aff comes from three running sums
  *     instead of a second pass over lam,t,dlam,dt;
  *   - fewer bytes again where the dynamics are the same at every stage: the two forward sweeps keep [B A]' in registers
- *     across the stages of a tile found stage-invariant (88 of the 153 / 228 doubles a C2 stage of these sweeps moves), see
+ *     across the stages of a tile found stage-invariant (88 of the 153 / 228 doubles a C2 stage of these sweeps moves), and a
+ *     batch whose tiles are ALL found so runs its rhs-only sweeps on kh_backrhs, which holds the block too (88 of 197), see
  *     "HELD DYNAMICS" below; kb_factor (row chunks at its register ceiling) and kb_backrhs fetch the block as before.
  * Equality-flagged rows (idxe) are not IPM rows here; their multipliers are recovered from
  * stationarity in kb_finalize.
@@ -261,9 +262,15 @@ __device__ static inline Acc acc_at(GArr arr, size_t e0, int i)
  * instances it carries.  The host zeroes the counters in front of and behind the root loop (gpu_batch.hip, run_ipm): no
  * other launch of these kernels ever sees a flag older than the data.  GqpOpts::hold bit 0 off (option hold_dynamics 0, every
  * sub-level): every tile fetches at every stage.
- *   NOT kb_backrhs, whose code is untouched: holding its block was measured twice and cost the tiles that fetch at every stage
- * (time-varying dynamics) -- the block fetched into a carried array under a branch at the top of the stage + 0.04 ms per launch,
- * the product branched on the flag 2.06 against 1.11 ms per launch (profiles/NOTES.md, "stage-invariant [B A]'"). */
+ *   The rhs-only backward sweep has TWO ENTRIES, chosen by the host per launch and not by the kernel per tile.  kb_backrhs fetches
+ * the block at every stage; its code is untouched, because a decision inside the kernel was measured twice and cost the tiles that
+ * fetch (time-varying dynamics): the block fetched into a carried array under a branch on the tile's flag + 0.04 ms per launch, the
+ * product branched on the flag 2.06 against 1.11 ms per launch (profiles/NOTES.md, "stage-invariant [B A]'").  kh_backrhs (behind
+ * kb_backrhs; instantiated where kb_hold<NX, NU, false>()) keeps the block in a loop-carried register array: its loop runs
+ * k = N .. 0, it fetches the block at the zero slot N (whose contents are 0) and at stage N-1, and the stages N-2 .. 0 reuse what
+ * stage N-1 returned.  It reads no flag: run_ipm (gpu_batch.hip) launches it -- redo 0 and redo 1 alike -- only from the root loop,
+ * once the detector's counters have been summed and EVERY tile of the batch is held; a mixed batch, the iteration that detects,
+ * sub-levels, the tail, sensitivities and hold_dynamics 0 run kb_backrhs.  Scalar "rhs_held_launches" counts its launches. */
 template <int NX, int NU, bool XBOX>
 constexpr bool kb_hold()
 {
@@ -679,6 +686,109 @@ __global__ void __launch_bounds__(64) kb_backrhs(GqpDev D, GqpOpts O, int redo)
             UNROLL for (int c = 0; c <= r; c++) Lx[PK(r, c)] = L[PK(NU + r, NU + c)];
         }
     }
+}
+
+/* The same sweep for a launch in which EVERY tile is held (see "HELD DYNAMICS"; the host's choice, run_ipm): [B A]' in a loop-carried
+ * register array, fetched in front of the stage's other loads at the zero slot N and at stage N-1 and reused by the stages
+ * N-2 .. 0 -- one branch on the scalar stage counter, no tile flag, no read of GqpDev::tile_inv.  Everything else is kb_backrhs
+ * without its XBOX phases, row for row in the same order of operations: every output is bit for bit what kb_backrhs writes.  A
+ * kernel of its own and not a shared body: with the body shared, kb_backrhs<8, 3, false> no longer compiled to the instruction
+ * stream it had (profiles/NOTES.md), and the tiles that fetch must not pay. */
+template <int NX, int NU>
+__global__ void __launch_bounds__(64) kh_backrhs(GqpDev D, GqpOpts O, int redo)
+{
+    constexpr int n = NX + NU, NP = n * (n + 1) / 2, NPX = NX * (NX + 1) / 2, NB = NU;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D.B) return;
+    const bool run = D.status[i] == GQP_RUNNING;
+    if (redo ? !(run && D.alpha[i] < 0.0) : !GQP_WAVE_ANY(run)) return;
+    const double smu = D.smu[i];
+    const double pscale = redo ? 0.0 : 1.0; /* redo = centering only: drop dlam_aff*dt_aff */
+
+    double Lx[NPX], lx[NX];
+    UNROLL for (int e = 0; e < NPX; e++) Lx[e] = 0.0;
+    UNROLL for (int c = 0; c < NX; c++) lx[c] = 0.0;
+    double bat[n * NX]; /* carried from stage to stage */
+    UNROLL for (int e = 0; e < n * NX; e++) bat[e] = 0.0;
+
+    for (int k = D.N; k >= 0; k--)
+    {
+        const StageU S = stage_u(D.st, k);
+        const uint64_t imask = S.bmask & ~S.emask;
+        const uint64_t am = GAT(D.amask, k);
+        const int nbg = S.nb;
+
+        if (k >= D.N - 1)
+        {
+            const Acc aB = ACC(D.BAt, k * n * NX);
+            UNROLL for (int e = 0; e < n * NX; e++) bat[e] = aB.ldj(0, e);
+        }
+        double rb[NX], gt[n];
+        UNROLL for (int c = 0; c < NX; c++) rb[c] = ACC(D.rb, 0).ld(k * NX + c);
+        UNROLL for (int j = 0; j < n; j++) gt[j] = ACC(D.rg, 0).ld(k * n + j);
+        UNROLL for (int j = 0; j < NB; j++)
+        {
+            GQP_ROW(j, has, ib);
+            const int el = S.o_ct + ib, eu = el + nbg;
+            const double laml = ACC(D.lam, 0).ld(el), lamu = ACC(D.lam, 0).ld(eu);
+            const double tl = ACC(D.t, 0).ld(el), tu = ACC(D.t, 0).ld(eu);
+            const double rdl = ACC(D.rd, 0).ld(el), rdu = ACC(D.rd, 0).ld(eu);
+            const double pl = ACC(D.pcorr, 0).ld(el), pu = ACC(D.pcorr, 0).ld(eu);
+            const bool al = has && ((am >> ib) & 1), au = has && ((am >> (nbg + ib)) & 1);
+            const double ll = al ? laml : 0.0, lu = au ? lamu : 0.0;
+            const double ttl = al ? tl : 1.0, ttu = au ? tu : 1.0;
+            const double rml = al ? ll * ttl - O.tau_min + pscale * pl - smu : 0.0;
+            const double rmu = au ? lu * ttu - O.tau_min + pscale * pu - smu : 0.0;
+            const double dl = al ? rdl : 0.0, du = au ? rdu : 0.0;
+            gt[j] += (rml + ll * dl) * frcp(ttl) - (rmu + lu * du) * frcp(ttu);
+        }
+        /* y = Lx+ (Lx+' rb + lx+) ; m = gt + BAt y */
+        double w0[NX], y[NX];
+        UNROLL for (int c = 0; c < NX; c++)
+        {
+            double a = lx[c];
+            UNROLL for (int q = c; q < NX; q++) a += Lx[PK(q, c)] * rb[q];
+            w0[c] = a;
+        }
+        UNROLL for (int r = 0; r < NX; r++)
+        {
+            double a = 0.0;
+            UNROLL for (int c = 0; c <= r; c++) a += Lx[PK(r, c)] * w0[c];
+            y[r] = a;
+        }
+        UNROLL for (int r = 0; r < n; r++)
+        {
+            double a = 0.0;
+            UNROLL for (int c = 0; c < NX; c++) a += bat[r * NX + c] * y[c];
+            gt[r] += a;
+        }
+        UNROLL for (int r = 0; r < n; r++) if ((S.emask >> r) & 1) gt[r] = 0.0;
+        /* (eight elements share one scalar offset: with one offset per element, computed ahead of the product, the allocator
+         * parked 34 of them in spilled scalar registers beside the held block) */
+        double L[NP];
+        UNROLL for (int e = 0; e < NP; e++) L[e] = ACC(D.Lf, 0).ldj(k * NP, e);
+        UNROLL for (int r = 0; r < n; r++)
+        {
+            double a = gt[r];
+            UNROLL for (int c = 0; c < r; c++) a -= L[PK(r, c)] * gt[c];
+            const double d = L[PK(r, r)];
+            gt[r] = d != 0.0 ? a * frcp(d) : 0.0;
+            ACC(D.lf, 0).st(k * n + r, gt[r]);
+        }
+        UNROLL for (int r = 0; r < NX; r++)
+        {
+            lx[r] = gt[NU + r];
+            UNROLL for (int c = 0; c <= r; c++) Lx[PK(r, c)] = L[PK(NU + r, NU + c)];
+        }
+    }
+}
+
+/* the held entry of a shape, null where the block does not fit beside the stage (kb_hold) */
+template <int NX, int NU>
+constexpr auto kh_backrhs_for() -> void (*)(GqpDev, GqpOpts, int)
+{
+    if constexpr (kb_hold<NX, NU, false>()) return kh_backrhs<NX, NU>;
+    else return nullptr;
 }
 
 /* ----------------------------------------------------------------- forward */

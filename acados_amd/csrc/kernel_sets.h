@@ -27,6 +27,9 @@ struct KernelSet
     kern_plain_t box_finalize;
     /* the ipm_kernels_box.hpp kernels for every shape (ACADOS_AMD_KB_SMALL=0: cross-check of the small-block kernels) */
     kern_redo_t kb_fact[2], kb_rhs[2], kb_fwd_aff[2], kb_fwd_corr[2];
+    /* the rhs-only sweep with [B A]' held across the stages (gqp::kh_backrhs, no XBOX), for launches in which every tile is held:
+     * beside box_rhs[0] (null where the small-block kernels serve the shape) and beside kb_rhs[0]; null where not instantiated */
+    kern_redo_t box_rhs_held, kb_rhs_held;
 };
 
 #define GQP_KSET(NX, NU, NG, NS)                                                               \
@@ -41,7 +44,8 @@ struct KernelSet
      {gqp::kb_factor<NX, NU, false>, gqp::kb_factor<NX, NU, true>},                            \
      {gqp::kb_backrhs<NX, NU, false>, gqp::kb_backrhs<NX, NU, true>},                          \
      {gqp::kb_forward<NX, NU, false, false>, gqp::kb_forward<NX, NU, true, false>},            \
-     {gqp::kb_forward<NX, NU, false, true>, gqp::kb_forward<NX, NU, true, true>}}
+     {gqp::kb_forward<NX, NU, false, true>, gqp::kb_forward<NX, NU, true, true>},              \
+     gqp::KbSmall<NX, NU>::value ? nullptr : gqp::kh_backrhs_for<NX, NU>(), gqp::kh_backrhs_for<NX, NU>()}
 
 /* partial condensing: parent shape (NX, NU), blocks of at most BSMAX stages -> child shape
  * (NX, BSMAX*NU); kernels in pcond_kernels.hpp */
