@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <climits>
 #include <vector>
@@ -132,6 +133,27 @@ struct SubBatch
     int cap = 0;           /* instances `c` was made for */
 };
 
+/* Blobs: all QP data / a whole iterate / every seed of every instance as ONE instance-major array, moved by one copy and one
+ * launch per direction ("Blobs"; the bulk section below).  One map per kind, built on first use (blob_map); what a
+ * kind consists of is its row of k_blobs.  Every kind's map carries every pointer: d_sgn / d_elem2 are filled for BLOB_SEED only
+ * and d_moff / d_mstage / d_mbit are empty tables where a kind has no mask entry (nm == 0) -- a member per kind would take a
+ * variant or a second struct beside the array of maps, more than the two null pointers cost */
+enum BlobKind { BLOB_IN, BLOB_OUT, BLOB_VEC, BLOB_SEED, BLOB_KINDS };
+struct BulkMap
+{
+    bool built = false;
+    int len = 0, nm = 0;
+    std::vector<std::string> fields; /* per segment */
+    std::vector<int> seg_stage, seg_off, seg_len;
+    std::vector<int> arr, elem;      /* per entry: array of T (-1: none) and element in it; d_arr / d_elem are these (grad_build reads them) */
+    int *d_arr = nullptr, *d_elem = nullptr, *d_moff = nullptr, *d_mstage = nullptr, *d_mbit = nullptr;
+    int *d_sgn = nullptr, *d_elem2 = nullptr; /* seed blob only: sign of the entry in the residual arrays, slot in sfix */
+    int *d_arr_g = nullptr, *d_elem_g = nullptr; /* READ direction: d_arr / d_elem themselves, except for the input blob
+                                                    (_get_bulk_in): the strict upper triangles of Q and R (not written: only the
+                                                    lower triangle of the caller's block is valid) are read from the mirrored element */
+    gqp::GArrTable T;
+};
+
 struct ocp_qp_gpu_batch
 {
     int B = 0, Bp = 0, N = 0, device = 0;
@@ -190,8 +212,8 @@ struct ocp_qp_gpu_batch
     double *d_stage = nullptr; /* staging for host->device field blocks */
     double *d_chunks = nullptr; /* the input blob handed over in pieces (_set_bulk_chunk): its own buffer -- d_stage is reused by */
     size_t chunks_cap = 0;      /* every other transfer (a hot start's _set_bulk_out comes between the chunks and the scatter) */
-    /* zero-copy gather (ocp_qp_gpu_batch_gather_tables / _gather_run): word tables of the full input blob [0] and of its vector part [1] */
-    struct GatherTab { int P = 0, n_words = 0, full = 0; int *d_slot = nullptr, *d_off = nullptr, *d_pos = nullptr; unsigned char *d_neg = nullptr; } gtab[2];
+    /* zero-copy gather (ocp_qp_gpu_batch_gather_tables / _gather_run): word tables of the full input blob [BLOB_IN] and of its vector part [BLOB_VEC] */
+    struct GatherTab { int P = 0, n_words = 0, full = 0; int *d_slot = nullptr, *d_off = nullptr, *d_pos = nullptr; unsigned char *d_neg = nullptr; } gtab[BLOB_KINDS];
     const double **d_gptrs = nullptr;
     size_t gptrs_cap = 0;
     long chunks_got = 0;        /* instances handed over since the last _set_bulk_staged (it refuses to scatter a partial blob) */
@@ -267,19 +289,7 @@ struct ocp_qp_gpu_batch
     /* KKT residuals of the current (data, iterate) on demand (res_kernels.hpp) */
     gqp::ResOut R = {{nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, nullptr, 0};
     /* bulk pack / unpack (one H2D + one launch per direction) */
-    struct BulkMap
-    {
-        bool built = false;
-        int len = 0, nm = 0;
-        std::vector<std::string> fields; /* per segment */
-        std::vector<int> seg_stage, seg_off, seg_len;
-        int *d_arr = nullptr, *d_elem = nullptr, *d_moff = nullptr, *d_mstage = nullptr, *d_mbit = nullptr;
-        int *d_sgn = nullptr, *d_elem2 = nullptr; /* seed blob only: sign of the entry in the residual arrays, slot in sfix */
-        int *d_arr_g = nullptr, *d_elem_g = nullptr; /* input blob, READ direction (_get_bulk_in): the strict upper triangles of
-                                                        Q and R (not written: only the lower triangle of the caller's block is
-                                                        valid) are read from the mirrored element */
-        gqp::GArrTable T;
-    } bulk_in, bulk_out, bulk_seed, bulk_vec;
+    BulkMap blob[BLOB_KINDS];
     /* reverse-mode data gradients (grad_kernels.hpp): op table over the input blob, gather / gate table of the output blob,
      * cotangent scatter table, the cotangent itself in the ux layout (the fixed variables' own term) */
     struct GradMap
@@ -807,6 +817,58 @@ const double *stage_in(ocp_qp_gpu_batch *b, const double *data, size_t cnt, int 
     }
     HIPCHK(hipMemcpyAsync(b->d_stage, data, sizeof(double) * cnt, hipMemcpyHostToDevice, b->stream));
     return b->d_stage;
+}
+
+/* the other direction: where the launches write `cnt` doubles for the caller -- its own pointer where that is a device pointer,
+ * else the staging area; behind the launches stage_out_done copies to the caller, if there is a copy, and waits for the stream */
+double *stage_out(ocp_qp_gpu_batch *b, double *data, size_t cnt, int is_device)
+{
+    if (is_device) return data;
+    if (cnt > b->stage_cap)
+    {
+        b->stage_cap = cnt * 2;
+        b->d_stage = dalloc<double>(b, b->stage_cap);
+    }
+    return b->d_stage;
+}
+
+void stage_out_done(ocp_qp_gpu_batch *b, double *data, size_t cnt, int is_device)
+{
+    if (!is_device) HIPCHK(hipMemcpyAsync(data, b->d_stage, sizeof(double) * cnt, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+}
+
+/* a table built on the host as a device array that lives as long as the batch (blocking copy; an empty table is one zeroed element) */
+template <class T>
+T *upload(ocp_qp_gpu_batch *b, const T *h, size_t cnt)
+{
+    T *d = dalloc<T>(b, cnt);
+    if (cnt) HIPCHK(hipMemcpy(d, h, sizeof(T) * cnt, hipMemcpyHostToDevice));
+    return d;
+}
+
+template <class T>
+T *upload(ocp_qp_gpu_batch *b, const std::vector<T> &h) { return upload(b, h.data(), h.size()); }
+
+/* what the launches of `run` and the copies in front of them take on the stream since the event `started` was recorded (the
+ * first chunk of a staged round), waited for, added to time_pack */
+template <class F>
+void pack_timed_since(ocp_qp_gpu_batch *b, hipEvent_t started, F run)
+{
+    run();
+    HIPCHK(hipEventRecord(b->ev1, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, started, b->ev1));
+    b->time_pack += ms * 1e-3;
+}
+
+/* ... from here.  ev0 / ev1 are free outside a solve */
+template <class F>
+void pack_timed(ocp_qp_gpu_batch *b, F run)
+{
+    HIPCHK(hipEventRecord(b->ev0, b->stream));
+    pack_timed_since(b, b->ev0, run);
 }
 
 } // namespace
@@ -2452,16 +2514,10 @@ try
             if (mlen < 0) { fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_get: field %s not available at stage %d\n", f, k); return -1; }
             if (mlen == 0) return 0;
             const size_t mcnt = (size_t) b->B * mlen;
-            double *mdst = data;
-            if (!is_device)
-            {
-                if (mcnt > b->stage_cap) { b->stage_cap = mcnt * 2; b->d_stage = dalloc<double>(b, b->stage_cap); }
-                mdst = b->d_stage;
-            }
+            double *mdst = stage_out(b, data, mcnt, is_device);
             int *dmm = upload_map(b, map);
             hipLaunchKernelGGL(gqp::k_getmask, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, mdst, b->B, mlen, dmm, b->D.amask, k, b->AW);
-            if (!is_device) HIPCHK(hipMemcpyAsync(data, mdst, sizeof(double) * mcnt, hipMemcpyDeviceToHost, b->stream));
-            HIPCHK(hipStreamSynchronize(b->stream));
+            stage_out_done(b, data, mcnt, is_device);
             return 0;
         }
     }
@@ -2509,20 +2565,10 @@ try
     }
     if (len == 0) return 0;
     const size_t cnt = (size_t) b->B * len;
-    double *dst = data;
-    if (!is_device)
-    {
-        if (cnt > b->stage_cap)
-        {
-            b->stage_cap = cnt * 2;
-            b->d_stage = dalloc<double>(b, b->stage_cap);
-        }
-        dst = b->d_stage;
-    }
+    double *dst = stage_out(b, data, cnt, is_device);
     int *dm = upload_map(b, map);
     hipLaunchKernelGGL(gqp::k_gather, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, dst, b->B, len, dm, arr);
-    if (!is_device) HIPCHK(hipMemcpyAsync(data, dst, sizeof(double) * cnt, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    stage_out_done(b, data, cnt, is_device);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
@@ -2782,109 +2828,171 @@ static const char *const k_bulk_out_fields[] = {"u", "x", "sl", "su", "pi", "lam
  * C2-shaped QP against 85 KB for the whole blob */
 static const char *const k_bulk_vec_fields[] = {"b", "q", "r", "lbu", "ubu", "lbx", "ubx", "lg", "ug", "zl", "zu", "lls", "lus", "lbu_mask", "ubu_mask",
                                                 "lbx_mask", "ubx_mask", "lg_mask", "ug_mask", "lls_mask", "lus_mask"};
+/* every seed of every instance (the batched eval_forw_sens / eval_adj_sens of the acados-side adapter; callers
+ * interfaces/acados_template/acados_template/c_templates_tera/acados_solver.in.c:3292-3337) */
+static const char *const k_seed_fields[] = {"r", "q", "zl", "zu", "b", "lbu", "lbx", "lg", "ubu", "ubx", "ug", "lls", "lus"};
 
-static void bulk_build(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch::BulkMap &M, const char *const *fields, int nf)
+/* The kinds of blob.  A new kind is a row here (+ its BlobKind): the field list in blob order, the prefix its segment names carry
+ * in the offset queries, whether its *_mask fields are bit segments of the activity words (k_bulk_masks / k_bulk_masks_get) and
+ * whether it is READ through a table pair of its own (d_arr_g / d_elem_g; else through the pair it is written by).  What one
+ * blob entry refers to is the element rule of blob_map, applied to the fields of the walk (blob_fields): a second table over an
+ * existing kind is another rule there */
+struct BlobDesc
 {
-    if (M.built) return;
-    finalize_structure(b);
-    const GqpDev &D = b->D;
-    const GArr table[16] = {D.BAt, D.bvec, D.RSQ, D.rq, D.dvec, D.DCt, D.Zz, D.ux, D.sv, D.pi, D.lam, D.t,
-                            {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}};
-    for (int q = 0; q < 16; q++) M.T.a[q] = table[q];
-    auto table_index = [&](const GArr &a) {
-        for (int q = 0; q < 12; q++) if (table[q].p == a.p) return q;
-        return -1;
-    };
-    std::vector<int> h_arr, h_elem, h_moff, h_mstage, h_mbit, h_arr_g, h_elem_g;
+    const char *const *fields;
+    int nf;
+    const char *prefix;
+    bool masks, read_map;
+};
+#define GQP_BLOB(fields, prefix, masks, read_map) {fields, (int) (sizeof(fields) / sizeof(fields[0])), prefix, masks, read_map}
+static const BlobDesc k_blobs[BLOB_KINDS] = {
+    /* BLOB_IN   */ GQP_BLOB(k_bulk_in_fields, "", true, true),
+    /* BLOB_OUT  */ GQP_BLOB(k_bulk_out_fields, "", false, false),
+    /* BLOB_VEC  */ GQP_BLOB(k_bulk_vec_fields, "", true, false),
+    /* BLOB_SEED */ GQP_BLOB(k_seed_fields, "seed_", false, false),
+};
+
+/* the public integers: `output` of _bulk_len / _bulk_offset is 0 for the input blob, 2 for its vector part and anything else for
+ * the output blob; `which` of the gather entries (has_out = false) is 2 for the vector part and anything else for the input blob */
+static BlobKind blob_kind(int v, bool has_out = true)
+{
+    if (v == 2) return BLOB_VEC;
+    return v && has_out ? BLOB_OUT : BLOB_IN;
+}
+
+/* one field of one stage as the walk hands it to the element rules */
+struct BlobField
+{
+    const char *f;
+    int k, len;
+    bool is_mask;
+    std::vector<int> map, map2; /* element of arr (arr2) per entry, -1: none; bit positions for a mask */
+    GArr arr = {nullptr, 0, 0}, arr2 = {nullptr, 0, 0};
+};
+
+static void blob_open_segment(BulkMap &M, const std::string &name, int k, int len)
+{
+    M.fields.push_back(name); M.seg_stage.push_back(k); M.seg_off.push_back((int) M.arr.size()); M.seg_len.push_back(len);
+}
+
+/* the layout of every kind: stage-major, the kind's field order, fields of length 0 at a stage skipped */
+static void blob_fields(ocp_qp_gpu_batch *b, const BlobDesc &K, const std::function<void(const BlobField &)> &visit)
+{
     for (int k = 0; k <= b->N; k++)
-        for (int fi = 0; fi < nf; fi++)
+        for (int fi = 0; fi < K.nf; fi++)
         {
-            const char *f = fields[fi];
-            std::vector<int> map, map2;
-            GArr arr = {nullptr, 0, 0}, arr2 = {nullptr, 0, 0};
-            const size_t flen = strlen(f);
-            int len;
-            const bool is_mask = flen > 5 && !strcmp(f + flen - 5, "_mask");
-            if (is_mask) len = mask_bits(b, f, k, map);
-            else len = field_map(b, f, k, map, &arr, &map2, &arr2);
-            if (len <= 0) continue;
-            M.fields.push_back(f); M.seg_stage.push_back(k); M.seg_off.push_back((int) h_arr.size()); M.seg_len.push_back(len);
-            for (int e = 0; e < len; e++)
+            BlobField s;
+            s.f = K.fields[fi]; s.k = k;
+            const size_t flen = strlen(s.f);
+            s.is_mask = K.masks && flen > 5 && !strcmp(s.f + flen - 5, "_mask");
+            if (s.is_mask) s.len = mask_bits(b, s.f, k, s.map);
+            else s.len = field_map(b, s.f, k, s.map, &s.arr, &s.map2, &s.arr2);
+            if (s.len > 0) visit(s);
+        }
+}
+
+/* the map of a kind, built on its first use */
+static BulkMap &blob_map(ocp_qp_gpu_batch *b, BlobKind kind) /* throws gqp_hip_failure: callers are inside a guarded entry */
+{
+    HIPCHK(hipSetDevice(b->device));
+    BulkMap &M = b->blob[kind];
+    if (M.built) return M;
+    finalize_structure(b);
+    const BlobDesc &K = k_blobs[kind];
+    const GqpDev &D = b->D;
+    if (kind == BLOB_SEED)
+    {
+        /* entry -> residual array (0 rg, 1 rgs, 2 rb, 3 rd: the table of _sens_set_bulk), element, sign there, slot in sfix */
+        std::vector<int> sgn, elem2;
+        blob_fields(b, K, [&](const BlobField &s) {
+            blob_open_segment(M, K.prefix + std::string(s.f), s.k, s.len);
+            const GqpStage &S = b->st[s.k];
+            const bool slack_grad = s.f[0] == 'z';
+            int a = -1, sg = 1;
+            if (slack_grad) a = 1;
+            else if (s.arr.p == D.rq.p) a = 0;
+            else if (s.arr.p == D.bvec.p) a = 2;
+            else if (s.arr.p == D.dvec.p) { a = 3; sg = (s.f[0] == 'l') ? -1 : 1; } /* lbu lbx lg lls lus: lower bounds */
+            for (int e = 0; e < s.len; e++)
             {
-                if (is_mask)
+                int el = s.map[e];
+                if (slack_grad) el = S.o_s + (s.f[1] == 'u' ? S.ns : 0) + e; /* rgs is indexed like sv */
+                M.arr.push_back(el >= 0 ? a : -1); M.elem.push_back(el >= 0 ? el : 0); sgn.push_back(sg);
+                elem2.push_back(s.arr2.p && s.map2[e] >= 0 ? s.map2[e] : -1);
+            }
+        });
+        M.d_sgn = upload(b, sgn); M.d_elem2 = upload(b, elem2);
+    }
+    else
+    {
+        /* entry -> array of the table below and element in it; a mask entry -> (position, stage, bit) */
+        const GArr table[16] = {D.BAt, D.bvec, D.RSQ, D.rq, D.dvec, D.DCt, D.Zz, D.ux, D.sv, D.pi, D.lam, D.t,
+                                {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}};
+        for (int q = 0; q < 16; q++) M.T.a[q] = table[q];
+        auto table_index = [&](const GArr &a) {
+            for (int q = 0; q < 12; q++) if (table[q].p == a.p) return q;
+            return -1;
+        };
+        std::vector<int> moff, mstage, mbit, arr_g, elem_g;
+        blob_fields(b, K, [&](const BlobField &s) {
+            blob_open_segment(M, K.prefix + std::string(s.f), s.k, s.len);
+            const int o = (int) M.arr.size();
+            for (int e = 0; e < s.len; e++)
+            {
+                if (s.is_mask)
                 {
-                    h_moff.push_back((int) h_arr.size()); h_mstage.push_back(k); h_mbit.push_back(map[e]);
-                    h_arr.push_back(-1); h_elem.push_back(0);
+                    moff.push_back(o + e); mstage.push_back(s.k); mbit.push_back(s.map[e]);
+                    M.arr.push_back(-1); M.elem.push_back(0);
                 }
                 else
                 {
-                    h_arr.push_back(map[e] >= 0 ? table_index(arr) : -1); h_elem.push_back(map[e] >= 0 ? map[e] : 0);
+                    M.arr.push_back(s.map[e] >= 0 ? table_index(s.arr) : -1); M.elem.push_back(s.map[e] >= 0 ? s.map[e] : 0);
                 }
             }
-            if (nf == 30) /* the input blob: read-direction map */
+            if (K.read_map)
             {
-                const bool sym = !strcmp(f, "Q") || !strcmp(f, "R");
-                const int dim = sym ? (f[0] == 'Q' ? b->nx[k] : b->nu[k]) : 0;
-                for (int e = 0; e < len; e++)
+                const bool sym = !strcmp(s.f, "Q") || !strcmp(s.f, "R");
+                const int dim = sym ? (s.f[0] == 'Q' ? b->nx[s.k] : b->nu[s.k]) : 0;
+                for (int e = 0; e < s.len; e++)
                 {
-                    int a = h_arr[h_arr.size() - len + e], el = h_elem[h_elem.size() - len + e];
+                    int a = M.arr[o + e], el = M.elem[o + e];
                     if (sym && a < 0)
                     {
                         const int r = e % dim, c = e / dim;       /* column-major, r < c here */
-                        const int m = map[r * dim + c];           /* element (c, r) */
-                        if (m >= 0) { a = table_index(arr); el = m; }
+                        const int m = s.map[r * dim + c];         /* element (c, r) */
+                        if (m >= 0) { a = table_index(s.arr); el = m; }
                     }
-                    h_arr_g.push_back(a); h_elem_g.push_back(el);
+                    arr_g.push_back(a); elem_g.push_back(el);
                 }
             }
-            if (arr2.p)
+            if (s.arr2.p)
             {
                 /* equality-flagged x bounds also define the value of the variable: a second, hidden
                  * segment that re-reads the same blob entries is not possible, so those entries are
                  * written through a duplicate segment placed right after (the caller's blob carries
                  * lbx twice: once as bound, once as value -- see ocp_qp_gpu_batch_bulk_offset) */
-                M.fields.push_back(std::string(f) + "#value"); M.seg_stage.push_back(k);
-                M.seg_off.push_back((int) h_arr.size()); M.seg_len.push_back(len);
-                for (int e = 0; e < len; e++)
+                blob_open_segment(M, std::string(s.f) + "#value", s.k, s.len);
+                for (int e = 0; e < s.len; e++)
                 {
-                    h_arr.push_back(map2[e] >= 0 ? table_index(arr2) : -1); h_elem.push_back(map2[e] >= 0 ? map2[e] : 0);
-                    if (nf == 30) { h_arr_g.push_back(h_arr.back()); h_elem_g.push_back(h_elem.back()); }
+                    M.arr.push_back(s.map2[e] >= 0 ? table_index(s.arr2) : -1); M.elem.push_back(s.map2[e] >= 0 ? s.map2[e] : 0);
+                    if (K.read_map) { arr_g.push_back(M.arr.back()); elem_g.push_back(M.elem.back()); }
                 }
             }
-        }
-    M.len = (int) h_arr.size();
-    M.nm = (int) h_moff.size();
-    M.d_arr = dalloc<int>(b, M.len); M.d_elem = dalloc<int>(b, M.len);
-    HIPCHK(hipMemcpy(M.d_arr, h_arr.data(), sizeof(int) * M.len, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(M.d_elem, h_elem.data(), sizeof(int) * M.len, hipMemcpyHostToDevice));
-    if (nf == 30 && M.len)
-    {
-        M.d_arr_g = dalloc<int>(b, M.len); M.d_elem_g = dalloc<int>(b, M.len);
-        HIPCHK(hipMemcpy(M.d_arr_g, h_arr_g.data(), sizeof(int) * M.len, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(M.d_elem_g, h_elem_g.data(), sizeof(int) * M.len, hipMemcpyHostToDevice));
+        });
+        M.nm = (int) moff.size();
+        if (K.read_map) { M.d_arr_g = upload(b, arr_g); M.d_elem_g = upload(b, elem_g); }
+        M.d_moff = upload(b, moff); M.d_mstage = upload(b, mstage); M.d_mbit = upload(b, mbit);
     }
-    M.d_moff = dalloc<int>(b, M.nm); M.d_mstage = dalloc<int>(b, M.nm); M.d_mbit = dalloc<int>(b, M.nm);
-    if (M.nm)
-    {
-        HIPCHK(hipMemcpy(M.d_moff, h_moff.data(), sizeof(int) * M.nm, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(M.d_mstage, h_mstage.data(), sizeof(int) * M.nm, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(M.d_mbit, h_mbit.data(), sizeof(int) * M.nm, hipMemcpyHostToDevice));
-    }
+    M.len = (int) M.arr.size();
+    M.d_arr = upload(b, M.arr); M.d_elem = upload(b, M.elem);
+    if (!M.d_arr_g) { M.d_arr_g = M.d_arr; M.d_elem_g = M.d_elem; }
     M.built = true;
+    return M;
 }
 
-static int gqp_bulk_len_impl(ocp_qp_gpu_batch *b, int output) /* throws gqp_hip_failure: callers are inside a guarded entry */
+/* position and length of one field at one stage; -1 / 0: not in the blob */
+static int blob_segment(const BulkMap &M, const char *field, int stage, int *len)
 {
-    HIPCHK(hipSetDevice(b->device));
-    auto &M = output == 2 ? b->bulk_vec : (output ? b->bulk_out : b->bulk_in);
-    bulk_build(b, M, output == 2 ? k_bulk_vec_fields : (output ? k_bulk_out_fields : k_bulk_in_fields), output == 2 ? 21 : (output ? 7 : 30));
-    return M.len;
-}
-
-static int gqp_bulk_offset_impl(ocp_qp_gpu_batch *b, int output, const char *field, int stage, int *len)
-{
-    gqp_bulk_len_impl(b, output);
-    auto &M = output == 2 ? b->bulk_vec : (output ? b->bulk_out : b->bulk_in);
     for (size_t q = 0; q < M.fields.size(); q++)
         if (M.seg_stage[q] == stage && M.fields[q] == field)
         {
@@ -2899,11 +3007,11 @@ static int gqp_bulk_offset_impl(ocp_qp_gpu_batch *b, int output, const char *fie
  * tables on the device (dalloc / hipMemcpy / hipFuncSetAttribute) -- where an out-of-memory error of a large batch shows up
  * first.  No exception crosses the C ABI: -1 (no valid length / offset is negative) */
 int ocp_qp_gpu_batch_bulk_len(ocp_qp_gpu_batch *b, int output)
-try { return gqp_bulk_len_impl(b, output); }
+try { return blob_map(b, blob_kind(output)).len; }
 catch (const gqp_hip_failure &) { return -1; }
 
 int ocp_qp_gpu_batch_bulk_offset(ocp_qp_gpu_batch *b, int output, const char *field, int stage, int *len)
-try { return gqp_bulk_offset_impl(b, output, field, stage, len); }
+try { return blob_segment(blob_map(b, blob_kind(output)), field, stage, len); }
 catch (const gqp_hip_failure &) { if (len) *len = 0; return -1; }
 
 #define GQP_MASK_SPC 4 /* stages per thread of k_bulk_masks */
@@ -2921,7 +3029,7 @@ static void bulk_gather_launch(ocp_qp_gpu_batch *b, double *dst, int len, const 
 
 /* blob (instance-major) -> the arrays of a bulk map: lanes along the elements where the destinations are instance-major too, through
  * an LDS tile where they are wave-tiled (ACADOS_AMD_SCATTER_PLAIN=1: one lane per instance, the cross-check) */
-static void bulk_scatter_launch(ocp_qp_gpu_batch *b, const double *src, int len, ocp_qp_gpu_batch::BulkMap &M)
+static void bulk_scatter_launch(ocp_qp_gpu_batch *b, const double *src, int len, BulkMap &M)
 {
     if (b->aos && !getenv("ACADOS_AMD_SCATTER_PLAIN"))
         hipLaunchKernelGGL(gqp::k_bulk_scatter_aos, dim3((len + 255) / 256, b->B), dim3(256), 0, b->stream, src, b->B, len, M.d_arr, M.d_elem, M.T);
@@ -2931,26 +3039,27 @@ static void bulk_scatter_launch(ocp_qp_gpu_batch *b, const double *src, int len,
         hipLaunchKernelGGL(gqp::k_bulk_scatter, dim3((b->B + 63) / 64, (len + 255) / 256), dim3(64), 0, b->stream, src, b->B, len, M.d_arr, M.d_elem, M.T);
 }
 
+/* a device-side blob of the kind of map M, BLOB_IN / BLOB_VEC (BLOB_OUT: no masks), into the batch: the scatter launch and, where
+ * the kind has mask entries, the launch that turns them into the activity words.  No wait, no timing: those are the caller's */
+static void blob_scatter(ocp_qp_gpu_batch *b, BulkMap &M, const double *src)
+{
+    bulk_scatter_launch(b, src, M.len, M);
+    if (M.nm)
+        hipLaunchKernelGGL(gqp::k_bulk_masks, dim3((b->B + 63) / 64, (b->N + 1 + GQP_MASK_SPC - 1) / GQP_MASK_SPC), dim3(64), 0, b->stream, src, b->B, M.len, M.d_moff,
+                           M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->AW, GQP_MASK_SPC);
+}
+
+/* the caller's blob of a kind: copy (where it is a host pointer) + scatter, timed and waited for */
+static void blob_set(ocp_qp_gpu_batch *b, BlobKind kind, const double *blob, int is_device)
+{
+    BulkMap &M = blob_map(b, kind);
+    pack_timed(b, [&] { blob_scatter(b, M, stage_in(b, blob, (size_t) b->B * M.len, is_device)); });
+}
+
 int ocp_qp_gpu_batch_set_bulk(ocp_qp_gpu_batch *b, const double *blob, int is_device)
 try
 {
-    const int len = gqp_bulk_len_impl(b, 0);
-    auto &M = b->bulk_in;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, b->stream));
-    const double *src = stage_in(b, blob, (size_t) b->B * len, is_device);
-    const dim3 block(64);
-    bulk_scatter_launch(b, src, len, M);
-    if (M.nm)
-        hipLaunchKernelGGL(gqp::k_bulk_masks, dim3((b->B + 63) / 64, (b->N + 1 + GQP_MASK_SPC - 1) / GQP_MASK_SPC), block, 0, b->stream, src, b->B, len, M.d_moff,
-                           M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->AW, GQP_MASK_SPC);
-    HIPCHK(hipEventRecord(e1, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    b->time_pack += ms * 1e-3;
-    HIPCHK(hipEventDestroy(e0)); HIPCHK(hipEventDestroy(e1));
+    blob_set(b, BLOB_IN, blob, is_device);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
@@ -2960,20 +3069,7 @@ catch (const gqp_hip_failure &) { return -1; }
 int ocp_qp_gpu_batch_set_bulk_vec(ocp_qp_gpu_batch *b, const double *blob, int is_device)
 try
 {
-    const int len = gqp_bulk_len_impl(b, 2);
-    auto &M = b->bulk_vec;
-    HIPCHK(hipEventRecord(b->ev0, b->stream));
-    const double *src = stage_in(b, blob, (size_t) b->B * len, is_device);
-    const dim3 block(64);
-    bulk_scatter_launch(b, src, len, M);
-    if (M.nm)
-        hipLaunchKernelGGL(gqp::k_bulk_masks, dim3((b->B + 63) / 64, (b->N + 1 + GQP_MASK_SPC - 1) / GQP_MASK_SPC), block, 0, b->stream, src, b->B, len, M.d_moff,
-                           M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->AW, GQP_MASK_SPC);
-    HIPCHK(hipEventRecord(b->ev1, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    b->time_pack += ms * 1e-3;
+    blob_set(b, BLOB_VEC, blob, is_device);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
@@ -3008,11 +3104,11 @@ int ocp_qp_gpu_batch_gather_tables(ocp_qp_gpu_batch *b, int which, int P, int n_
                                    const unsigned char *w_neg)
 try
 {
-    HIPCHK(hipSetDevice(b->device));
-    const int len = gqp_bulk_len_impl(b, which == 2 ? 2 : 0);
+    const BlobKind kind = blob_kind(which, false);
+    const int len = blob_map(b, kind).len;
     for (int w = 0; w < n_words; w++)
         if (w_slot[w] < 0 || w_slot[w] >= P || w_pos[w] < 0 || w_pos[w] >= len || w_off[w] < 0) return -1;
-    auto &G = b->gtab[which == 2 ? 1 : 0];
+    auto &G = b->gtab[kind];
     G.P = P; G.n_words = n_words;
     {
         /* do the words write EVERY position of the blob?  If not, the gather clears its buffer first: the positions no word writes
@@ -3022,51 +3118,44 @@ try
         for (int w = 0; w < n_words; w++) if (!seen[w_pos[w]]) { seen[w_pos[w]] = 1; covered++; }
         G.full = covered == len;
     }
-    G.d_slot = dalloc<int>(b, n_words); G.d_off = dalloc<int>(b, n_words); G.d_pos = dalloc<int>(b, n_words); G.d_neg = dalloc<unsigned char>(b, n_words);
-    if (n_words)
-    {
-        HIPCHK(hipMemcpy(G.d_slot, w_slot, sizeof(int) * n_words, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(G.d_off, w_off, sizeof(int) * n_words, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(G.d_pos, w_pos, sizeof(int) * n_words, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(G.d_neg, w_neg, n_words, hipMemcpyHostToDevice));
-    }
+    G.d_slot = upload(b, w_slot, n_words); G.d_off = upload(b, w_off, n_words); G.d_pos = upload(b, w_pos, n_words); G.d_neg = upload(b, w_neg, n_words);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
+
+/* the buffer of the device-side input blob (chunk protocol and zero-copy gather; one for both blobs: the full one is the longer).
+ * B * len is fixed for a batch: exactly that.  True where it was allocated here: nothing of a round is in it */
+static bool chunks_reserve(ocp_qp_gpu_batch *b)
+{
+    const size_t cnt = (size_t) b->B * blob_map(b, BLOB_IN).len;
+    if (cnt <= b->chunks_cap) return false;
+    HIPCHK(hipStreamSynchronize(b->stream)); /* (only ever on the first use by a batch: nothing of it is in flight yet) */
+    b->chunks_cap = cnt;
+    b->d_chunks = dalloc<double>(b, b->chunks_cap);
+    return true;
+}
 
 int ocp_qp_gpu_batch_gather_run(ocp_qp_gpu_batch *b, int which, const void *const *ptrs)
 try
 {
     HIPCHK(hipSetDevice(b->device));
-    auto &G = b->gtab[which == 2 ? 1 : 0];
+    const BlobKind kind = blob_kind(which, false);
+    auto &G = b->gtab[kind];
     if (G.n_words <= 0 || G.P <= 0) return -1;
-    const int len = gqp_bulk_len_impl(b, which == 2 ? 2 : 0);
-    const size_t cnt = (size_t) b->B * gqp_bulk_len_impl(b, 0); /* (one buffer for both blobs: the full one is the longer) */
-    if (cnt > b->chunks_cap)
-    {
-        HIPCHK(hipStreamSynchronize(b->stream));
-        b->chunks_cap = cnt;
-        b->d_chunks = dalloc<double>(b, b->chunks_cap);
-    }
+    BulkMap &M = blob_map(b, kind);
+    const int len = M.len;
+    chunks_reserve(b);
     const size_t np = (size_t) b->B * G.P;
     if (np > b->gptrs_cap) { b->gptrs_cap = np; b->d_gptrs = dalloc<const double *>(b, np); }
-    hipEvent_t g0, g1;
-    HIPCHK(hipEventCreate(&g0)); HIPCHK(hipEventCreate(&g1));
-    const double tp = b->time_pack;
-    HIPCHK(hipEventRecord(g0, b->stream));
-    HIPCHK(hipMemcpyAsync(b->d_gptrs, ptrs, sizeof(void *) * np, hipMemcpyHostToDevice, b->stream));
-    if (!G.full) HIPCHK(hipMemsetAsync(b->d_chunks, 0, sizeof(double) * (size_t) b->B * (size_t) len, b->stream));
-    hipLaunchKernelGGL(gqp::k_gather_host, dim3((G.n_words + 255) / 256, b->B), dim3(256), 0, b->stream, (const double *const *) b->d_gptrs, G.P, b->B,
-                       G.n_words, (const int *) G.d_slot, (const int *) G.d_off, (const int *) G.d_pos, (const unsigned char *) G.d_neg, b->d_chunks, len);
-    b->chunks_got = 0; /* (the chunk protocol shares the buffer: a round in flight is void) */
-    const int rc = which == 2 ? ocp_qp_gpu_batch_set_bulk_vec(b, b->d_chunks, 1) : ocp_qp_gpu_batch_set_bulk(b, b->d_chunks, 1);
-    HIPCHK(hipEventRecord(g1, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, g0, g1));
-    b->time_pack = tp + ms * 1e-3; /* gather + scatter */
-    HIPCHK(hipEventDestroy(g0)); HIPCHK(hipEventDestroy(g1));
-    return rc;
+    pack_timed(b, [&] { /* pointer copy + gather + scatter */
+        HIPCHK(hipMemcpyAsync(b->d_gptrs, ptrs, sizeof(void *) * np, hipMemcpyHostToDevice, b->stream));
+        if (!G.full) HIPCHK(hipMemsetAsync(b->d_chunks, 0, sizeof(double) * (size_t) b->B * (size_t) len, b->stream));
+        hipLaunchKernelGGL(gqp::k_gather_host, dim3((G.n_words + 255) / 256, b->B), dim3(256), 0, b->stream, (const double *const *) b->d_gptrs, G.P, b->B,
+                           G.n_words, (const int *) G.d_slot, (const int *) G.d_off, (const int *) G.d_pos, (const unsigned char *) G.d_neg, b->d_chunks, len);
+        b->chunks_got = 0; /* (the chunk protocol shares the buffer: a round in flight is void) */
+        blob_scatter(b, M, b->d_chunks);
+    });
+    return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
 
@@ -3077,16 +3166,9 @@ catch (const gqp_hip_failure &) { return -1; }
 int ocp_qp_gpu_batch_set_bulk_chunk(ocp_qp_gpu_batch *b, const double *blob_chunk, int first, int count)
 try
 {
-    const int len = gqp_bulk_len_impl(b, 0);
+    const int len = blob_map(b, BLOB_IN).len;
     if (first < 0 || count < 0 || first + count > b->B) return -1;
-    const size_t cnt = (size_t) b->B * len;
-    if (cnt > b->chunks_cap)
-    {
-        HIPCHK(hipStreamSynchronize(b->stream)); /* (only ever on the first chunk of a batch: nothing of it is in flight yet) */
-        b->chunks_cap = cnt; /* B * len is fixed for a batch: exactly that */
-        b->d_chunks = dalloc<double>(b, b->chunks_cap);
-        b->chunks_got = 0;
-    }
+    if (chunks_reserve(b)) b->chunks_got = 0;
     if (b->chunks_got == 0)
     {
         if (!b->chunks_ev) HIPCHK(hipEventCreate(&b->chunks_ev));
@@ -3102,9 +3184,8 @@ catch (const gqp_hip_failure &) { return -1; }
 int ocp_qp_gpu_batch_set_bulk_staged(ocp_qp_gpu_batch *b)
 try
 {
-    const int len = gqp_bulk_len_impl(b, 0);
-    auto &M = b->bulk_in;
-    if ((size_t) b->B * len > b->chunks_cap) return -1; /* no chunk was ever handed over */
+    BulkMap &M = blob_map(b, BLOB_IN);
+    if ((size_t) b->B * M.len > b->chunks_cap) return -1; /* no chunk was ever handed over */
     /* every instance must have arrived in THIS round: a missing range would scatter the previous call's data for those instances
      * (ranges are the caller's to keep disjoint: the count is what can be checked here) */
     const long got = b->chunks_got;
@@ -3114,16 +3195,7 @@ try
         fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_set_bulk_staged: %ld of %d instances were handed over since the last scatter\n", got, b->B);
         return -1;
     }
-    const dim3 block(64);
-    bulk_scatter_launch(b, (const double *) b->d_chunks, len, M);
-    if (M.nm)
-        hipLaunchKernelGGL(gqp::k_bulk_masks, dim3((b->B + 63) / 64, (b->N + 1 + GQP_MASK_SPC - 1) / GQP_MASK_SPC), block, 0, b->stream, (const double *) b->d_chunks, b->B, len, M.d_moff,
-                           M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->AW, GQP_MASK_SPC);
-    HIPCHK(hipEventRecord(b->ev1, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, b->chunks_ev, b->ev1));
-    b->time_pack += ms * 1e-3;
+    pack_timed_since(b, b->chunks_ev, [&] { blob_scatter(b, M, b->d_chunks); }); /* first chunk ... scatter */
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
@@ -3134,22 +3206,14 @@ catch (const gqp_hip_failure &) { return -1; }
 int ocp_qp_gpu_batch_get_bulk_in(ocp_qp_gpu_batch *b, double *blob, int is_device)
 try
 {
-    const int len = gqp_bulk_len_impl(b, 0);
-    auto &M = b->bulk_in;
-    const size_t cnt = (size_t) b->B * len;
-    double *dst = blob;
-    if (!is_device)
-    {
-        if (cnt > b->stage_cap) { b->stage_cap = cnt * 2; b->d_stage = dalloc<double>(b, b->stage_cap); }
-        dst = b->d_stage;
-    }
-    const dim3 grid((b->B + 63) / 64, (len + 255) / 256), block(64);
-    bulk_gather_launch(b, dst, len, M.d_arr_g, M.d_elem_g, M.T);
+    BulkMap &M = blob_map(b, BLOB_IN);
+    const size_t cnt = (size_t) b->B * M.len;
+    double *dst = stage_out(b, blob, cnt, is_device);
+    bulk_gather_launch(b, dst, M.len, M.d_arr_g, M.d_elem_g, M.T);
     if (M.nm)
-        hipLaunchKernelGGL(gqp::k_bulk_masks_get, dim3((b->B + 63) / 64), block, 0, b->stream, dst, b->B, len, M.d_moff,
+        hipLaunchKernelGGL(gqp::k_bulk_masks_get, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, dst, b->B, M.len, M.d_moff,
                            M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->AW);
-    if (!is_device) HIPCHK(hipMemcpyAsync(blob, dst, sizeof(double) * cnt, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    stage_out_done(b, blob, cnt, is_device);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
@@ -3159,125 +3223,56 @@ catch (const gqp_hip_failure &) { return -1; }
 int ocp_qp_gpu_batch_set_bulk_out(ocp_qp_gpu_batch *b, const double *blob, int is_device)
 try
 {
-    const int len = gqp_bulk_len_impl(b, 1);
-    auto &M = b->bulk_out;
-    const double *src = stage_in(b, blob, (size_t) b->B * len, is_device);
-    bulk_scatter_launch(b, src, len, M);
+    BulkMap &M = blob_map(b, BLOB_OUT);
+    blob_scatter(b, M, stage_in(b, blob, (size_t) b->B * M.len, is_device));
     HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
 
+/* the OUTPUT blob read from the solution arrays, or (directions) through the same element maps from the direction arrays of the
+ * last _sens_solve */
+static void blob_get_out(ocp_qp_gpu_batch *b, double *blob, int is_device, bool directions)
+{
+    BulkMap &M = blob_map(b, BLOB_OUT);
+    gqp::GArrTable T = M.T;
+    const GqpDev &D = b->D;
+    if (directions) { T.a[7] = D.dux; T.a[8] = D.dsv; T.a[9] = D.dpi; T.a[10] = D.dlam; T.a[11] = D.dt; }
+    const size_t cnt = (size_t) b->B * M.len;
+    bulk_gather_launch(b, stage_out(b, blob, cnt, is_device), M.len, M.d_arr_g, M.d_elem_g, T);
+    stage_out_done(b, blob, cnt, is_device);
+}
+
 int ocp_qp_gpu_batch_get_bulk(ocp_qp_gpu_batch *b, double *blob, int is_device)
 try
 {
-    const int len = gqp_bulk_len_impl(b, 1);
-    auto &M = b->bulk_out;
-    const size_t cnt = (size_t) b->B * len;
-    double *dst = blob;
-    if (!is_device)
-    {
-        if (cnt > b->stage_cap) { b->stage_cap = cnt * 2; b->d_stage = dalloc<double>(b, b->stage_cap); }
-        dst = b->d_stage;
-    }
-    const dim3 grid((b->B + 63) / 64, (len + 255) / 256), block(64);
-    bulk_gather_launch(b, dst, len, M.d_arr, M.d_elem, M.T);
-    if (!is_device) HIPCHK(hipMemcpyAsync(blob, dst, sizeof(double) * cnt, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    blob_get_out(b, blob, is_device, false);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
 
 /* ---- bulk seeds / sensitivities: every seed of every instance in one host->device copy and one launch, every
- * direction back in one launch and one copy (the batched eval_forw_sens / eval_adj_sens of the acados-side adapter;
- * callers interfaces/acados_template/acados_template/c_templates_tera/acados_solver.in.c:3292-3337) ---- */
-static const char *const k_seed_fields[] = {"r", "q", "zl", "zu", "b", "lbu", "lbx", "lg", "ubu", "ubx", "ug", "lls", "lus"};
-
-static void seed_build(ocp_qp_gpu_batch *b)
-{
-    auto &M = b->bulk_seed;
-    if (M.built) return;
-    finalize_structure(b);
-    const GqpDev &D = b->D;
-    std::vector<int> h_arr, h_elem, h_sgn, h_elem2;
-    for (int k = 0; k <= b->N; k++)
-        for (const char *f : k_seed_fields)
-        {
-            std::vector<int> map, map2;
-            GArr arr = {nullptr, 0, 0}, arr2 = {nullptr, 0, 0};
-            const int len = field_map(b, f, k, map, &arr, &map2, &arr2);
-            if (len <= 0) continue;
-            const GqpStage &S = b->st[k];
-            const bool slack_grad = f[0] == 'z';
-            int a = -1, sgn = 1;
-            if (slack_grad) a = 1;
-            else if (arr.p == D.rq.p) a = 0;
-            else if (arr.p == D.bvec.p) a = 2;
-            else if (arr.p == D.dvec.p) { a = 3; sgn = (f[0] == 'l') ? -1 : 1; } /* lbu lbx lg lls lus: lower bounds */
-            M.fields.push_back(std::string("seed_") + f); M.seg_stage.push_back(k);
-            M.seg_off.push_back((int) h_arr.size()); M.seg_len.push_back(len);
-            for (int e = 0; e < len; e++)
-            {
-                int el = map[e];
-                if (slack_grad) el = S.o_s + (f[1] == 'u' ? S.ns : 0) + e; /* rgs is indexed like sv */
-                h_arr.push_back(el >= 0 ? a : -1); h_elem.push_back(el >= 0 ? el : 0); h_sgn.push_back(sgn);
-                h_elem2.push_back(arr2.p && map2[e] >= 0 ? map2[e] : -1);
-            }
-        }
-    M.len = (int) h_arr.size();
-    M.d_arr = dalloc<int>(b, M.len); M.d_elem = dalloc<int>(b, M.len); M.d_sgn = dalloc<int>(b, M.len); M.d_elem2 = dalloc<int>(b, M.len);
-    if (M.len)
-    {
-        HIPCHK(hipMemcpy(M.d_arr, h_arr.data(), sizeof(int) * M.len, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(M.d_elem, h_elem.data(), sizeof(int) * M.len, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(M.d_sgn, h_sgn.data(), sizeof(int) * M.len, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(M.d_elem2, h_elem2.data(), sizeof(int) * M.len, hipMemcpyHostToDevice));
-    }
-    M.built = true;
-}
-
-static int gqp_sens_bulk_len_impl(ocp_qp_gpu_batch *b, int output)
-{
-    if (output) return gqp_bulk_len_impl(b, 1);
-    HIPCHK(hipSetDevice(b->device));
-    seed_build(b);
-    return b->bulk_seed.len;
-}
-
-static int gqp_sens_bulk_offset_impl(ocp_qp_gpu_batch *b, int output, const char *field, int stage, int *len)
-{
-    if (output)
-    {
-        if (strncmp(field, "sens_", 5)) { if (len) *len = 0; return -1; }
-        return gqp_bulk_offset_impl(b, 1, field + 5, stage, len);
-    }
-    gqp_sens_bulk_len_impl(b, 0);
-    auto &M = b->bulk_seed;
-    for (size_t q = 0; q < M.fields.size(); q++)
-        if (M.seg_stage[q] == stage && M.fields[q] == field)
-        {
-            if (len) *len = M.seg_len[q];
-            return M.seg_off[q];
-        }
-    if (len) *len = 0;
-    return -1;
-}
-
+ * direction back in one launch and one copy (BLOB_SEED in, BLOB_OUT back) ---- */
 int ocp_qp_gpu_batch_sens_bulk_len(ocp_qp_gpu_batch *b, int output)
-try { return gqp_sens_bulk_len_impl(b, output); }
+try { return blob_map(b, output ? BLOB_OUT : BLOB_SEED).len; }
 catch (const gqp_hip_failure &) { return -1; }
 
 int ocp_qp_gpu_batch_sens_bulk_offset(ocp_qp_gpu_batch *b, int output, const char *field, int stage, int *len)
-try { return gqp_sens_bulk_offset_impl(b, output, field, stage, len); }
+try
+{
+    if (!output) return blob_segment(blob_map(b, BLOB_SEED), field, stage, len);
+    if (strncmp(field, "sens_", 5)) { if (len) *len = 0; return -1; }
+    return blob_segment(blob_map(b, BLOB_OUT), field + 5, stage, len);
+}
 catch (const gqp_hip_failure &) { if (len) *len = 0; return -1; }
 
 int ocp_qp_gpu_batch_sens_set_bulk(ocp_qp_gpu_batch *b, const double *blob, int is_device)
 try
 {
-    const int len = gqp_sens_bulk_len_impl(b, 0);
+    BulkMap &M = blob_map(b, BLOB_SEED);
+    const int len = M.len;
     if (sens_begin(b)) return -1; /* zeroes the seed arrays, factorises at the solution where the sweeps run in place */
     if (len == 0) return 0;
-    auto &M = b->bulk_seed;
     const GqpDev &D = b->D;
     const GArr table[5] = {D.rg, D.rgs, D.rb, D.rd, b->sfix};
     for (int q = 0; q < 16; q++) M.T.a[q] = q < 5 ? table[q] : GArr{nullptr, 0, 0};
@@ -3292,22 +3287,7 @@ catch (const gqp_hip_failure &) { return -1; }
 int ocp_qp_gpu_batch_sens_get_bulk(ocp_qp_gpu_batch *b, double *blob, int is_device)
 try
 {
-    const int len = gqp_bulk_len_impl(b, 1);
-    auto &M = b->bulk_out;
-    gqp::GArrTable T = M.T; /* same element maps as the solution, read from the direction arrays */
-    const GqpDev &D = b->D;
-    T.a[7] = D.dux; T.a[8] = D.dsv; T.a[9] = D.dpi; T.a[10] = D.dlam; T.a[11] = D.dt;
-    const size_t cnt = (size_t) b->B * len;
-    double *dst = blob;
-    if (!is_device)
-    {
-        if (cnt > b->stage_cap) { b->stage_cap = cnt * 2; b->d_stage = dalloc<double>(b, b->stage_cap); }
-        dst = b->d_stage;
-    }
-    const dim3 grid((b->B + 63) / 64, (len + 255) / 256), block(64);
-    bulk_gather_launch(b, dst, len, M.d_arr, M.d_elem, T);
-    if (!is_device) HIPCHK(hipMemcpyAsync(blob, dst, sizeof(double) * cnt, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    blob_get_out(b, blob, is_device, true);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
@@ -3317,18 +3297,13 @@ static void grad_build(ocp_qp_gpu_batch *b)
 {
     auto &G = b->grad;
     if (G.built) return;
-    const int len = gqp_bulk_len_impl(b, 0), olen = gqp_bulk_len_impl(b, 1);
-    const auto &Mi = b->bulk_in, &Mo = b->bulk_out;
+    const BulkMap &Mi = blob_map(b, BLOB_IN), &Mo = blob_map(b, BLOB_OUT);
+    const int len = Mi.len, olen = Mo.len;
     const int N = b->N, NX = b->ks->NX, NU = b->ks->NU, n = NX + NU, NP = n * (n + 1) / 2;
-    auto ob = [&](const char *f, int k) { int l = 0; const int o = gqp_bulk_offset_impl(b, 1, f, k, &l); return l > 0 ? o : -1; };
+    auto ob = [&](const char *f, int k) { int l = 0; const int o = blob_segment(Mo, f, k, &l); return l > 0 ? o : -1; };
     /* output blob: gather map renumbered to the kernel's tables, activity gates, cotangent destinations */
-    std::vector<int> oarr(olen, -1), oelem(olen, 0), ogate(olen, -1), ckind(olen, 0), celem(olen, 0);
-    {
-        std::vector<int> ha(olen), he(olen);
-        HIPCHK(hipMemcpy(ha.data(), Mo.d_arr, sizeof(int) * olen, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(he.data(), Mo.d_elem, sizeof(int) * olen, hipMemcpyDeviceToHost));
-        for (int e = 0; e < olen; e++) { oarr[e] = ha[e] >= 7 && ha[e] <= 11 ? ha[e] - 7 : -1; oelem[e] = he[e]; }
-    }
+    std::vector<int> oarr(olen, -1), oelem = Mo.elem, ogate(olen, -1), ckind(olen, 0), celem(olen, 0);
+    for (int e = 0; e < olen; e++) oarr[e] = Mo.arr[e] >= 7 && Mo.arr[e] <= 11 ? Mo.arr[e] - 7 : -1;
     for (size_t q = 0; q < Mo.fields.size(); q++)
     {
         const std::string &f = Mo.fields[q];
@@ -3422,16 +3397,11 @@ static void grad_build(ocp_qp_gpu_batch *b)
     G.len = len;
     G.olen = olen;
     G.lds = sizeof(double) * 2 * (size_t) olen;
-    G.d_ops = dalloc<gqp::GradOp>(b, len);
-    G.d_terms = dalloc<gqp::GradTerm>(b, terms.size());
-    G.d_oarr = dalloc<int>(b, olen); G.d_oelem = dalloc<int>(b, olen); G.d_ogate = dalloc<int>(b, olen);
-    G.d_ckind = dalloc<int>(b, olen); G.d_celem = dalloc<int>(b, olen);
+    G.d_ops = upload(b, ops);
+    G.d_terms = upload(b, terms);
+    G.d_oarr = upload(b, oarr); G.d_oelem = upload(b, oelem); G.d_ogate = upload(b, ogate);
+    G.d_ckind = upload(b, ckind); G.d_celem = upload(b, celem);
     G.d_bad = dalloc<int>(b, 1);
-    if (len) HIPCHK(hipMemcpy(G.d_ops, ops.data(), sizeof(gqp::GradOp) * len, hipMemcpyHostToDevice));
-    if (!terms.empty()) HIPCHK(hipMemcpy(G.d_terms, terms.data(), sizeof(gqp::GradTerm) * terms.size(), hipMemcpyHostToDevice));
-    const std::pair<int *, std::vector<int> *> up[] = {{G.d_oarr, &oarr}, {G.d_oelem, &oelem}, {G.d_ogate, &ogate}, {G.d_ckind, &ckind}, {G.d_celem, &celem}};
-    for (auto &u : up)
-        if (olen) HIPCHK(hipMemcpy(u.first, u.second->data(), sizeof(int) * olen, hipMemcpyHostToDevice));
     G.cot = garr<double>(b, (size_t) (N + 2) * n);
     if (G.lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *) gqp::k_data_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int) G.lds));
     G.built = true;
@@ -3487,12 +3457,7 @@ try
     G.seeded = false;
     if (ocp_qp_gpu_batch_sens_solve(b)) return -1; /* the adjoint direction, in dux dsv dpi dlam dt */
     const size_t cnt = (size_t) b->B * G.len;
-    double *dst = grad;
-    if (!is_device)
-    {
-        if (cnt > b->stage_cap) { b->stage_cap = cnt * 2; b->d_stage = dalloc<double>(b, b->stage_cap); }
-        dst = b->d_stage;
-    }
+    double *dst = stage_out(b, grad, cnt, is_device);
     const GqpDev &D = b->D;
     gqp::GArrTable T;
     const GArr tab[14] = {D.ux, D.sv, D.pi, D.lam, D.t, D.dux, D.dsv, D.dpi, D.dlam, D.dt, D.RSQ, D.BAt, D.DCt, G.cot};
@@ -3502,8 +3467,7 @@ try
         GQP_LAUNCH_COOP(gqp::k_data_grad, dim3(per * GQP_GRAD_XCD), dim3(GQP_GRAD_THREADS), G.lds, b->stream, dst, b->B, G.len, G.d_ops, G.d_terms,
                         G.olen, G.d_oarr, G.d_oelem, G.d_ogate, T, D.amask, D.status, per);
     HIPCHK(hipGetLastError());
-    if (!is_device) HIPCHK(hipMemcpyAsync(grad, dst, sizeof(double) * cnt, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    stage_out_done(b, grad, cnt, is_device);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }
@@ -3688,18 +3652,15 @@ static int gather_impl(ocp_qp_gpu_batch *b, ocp_qp_gpu_comm *c, int root, const 
         fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_gather: counts[%d] = %d but this rank's batch holds %d instances\n", c->rank, counts[c->rank], b->B);
         return -1;
     }
-    const int len = gqp_bulk_len_impl(b, 1);
-    auto &M = b->bulk_out;
+    BulkMap &M = blob_map(b, BLOB_OUT);
+    const int len = M.len;
     const size_t cnt = (size_t) b->B * len;
     /* send buffers: the solution blob of this rank (gather launch into the staging area), status / iter interleaved */
-    const size_t need = cnt + (size_t) b->B + 8; /* doubles: blob + room for 2*B ints + the time */
-    if (need > b->stage_cap) { b->stage_cap = need * 2; b->d_stage = dalloc<double>(b, b->stage_cap); }
-    double *blob = b->d_stage;
-    int *info = (int *) (b->d_stage + cnt);
-    double *tm = b->d_stage + cnt + b->B + 1;
-    const dim3 grid((b->B + 63) / 64, (len + 255) / 256), block(64);
-    bulk_gather_launch(b, blob, len, M.d_arr, M.d_elem, M.T);
-    hipLaunchKernelGGL(gqp::k_pack_info, dim3((b->B + 63) / 64), block, 0, b->stream, b->D, info);
+    double *blob = stage_out(b, nullptr, cnt + (size_t) b->B + 8, 0); /* doubles: blob + room for 2*B ints + the time */
+    int *info = (int *) (blob + cnt);
+    double *tm = blob + cnt + b->B + 1;
+    bulk_gather_launch(b, blob, len, M.d_arr_g, M.d_elem_g, M.T);
+    hipLaunchKernelGGL(gqp::k_pack_info, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, b->D, info);
     HIPCHK(hipMemcpyAsync(tm, &b->time_tot, sizeof(double), hipMemcpyHostToDevice, b->stream));
     bool even = true;
     if (counts) for (int r = 0; r < c->n; r++) even = even && counts[r] == b->B;
