@@ -266,6 +266,8 @@ struct ocp_qp_gpu_batch
     int hold_dynamics = 1;               /* option: 1 = tiles whose [B A]' is found stage-invariant keep it in registers, 0 = never */
     int n_tiles_invariant = 0;           /* tiles found so by the last solve */
     int n_rhs_held_launches = 0;         /* launches of the held rhs entry (IpmKernels::rhs_held) in the last solve */
+    int n_fact_held_launches = 0;        /* launches of the held factor entry (IpmKernels::fact_held) in the last solve */
+    hipEvent_t tiles_ev = nullptr;       /* recorded behind the read-back of the held-dynamics counters (run_ipm) */
     /* solution sensitivities / factor at the solution */
     bool factor_stale = false;           /* the last solve finished instances on a sub-level: Lf of the root is not theirs */
     bool sens_open = false;              /* seeds are being collected (rg, rb, rd hold seeds, not residuals) */
@@ -1150,6 +1152,7 @@ try
     (void) hipEventDestroy(b->ev0);
     (void) hipEventDestroy(b->ev1);
     if (b->chunks_ev) (void) hipEventDestroy(b->chunks_ev);
+    if (b->tiles_ev) (void) hipEventDestroy(b->tiles_ev);
     for (hipEvent_t e : b->prof_ev) (void) hipEventDestroy(e);
     (void) hipStreamDestroy(b->stream);
     if (b->child) ocp_qp_gpu_batch_destroy(b->child);
@@ -1633,6 +1636,7 @@ struct IpmKernels
 {
     kern_redo_t fact, rhs, faff, fcorr;
     kern_redo_t rhs_held; /* K.rhs with [B A]' held across the stages, for a launch whose tiles are all held; null: there is none */
+    kern_redo_t fact_held; /* K.fact likewise (static LDS of its own, none of shmem_fact) */
     kern_plain_t final_;
 };
 
@@ -1668,10 +1672,12 @@ static IpmKernels pick_kernels(const ocp_qp_gpu_batch *b)
     k.faff = b->use_box ? ks->box_fwd_aff[xb] : ks->fwd_aff;
     k.fcorr = b->use_box ? ks->box_fwd_corr[xb] : ks->fwd_corr;
     k.rhs_held = (b->use_box && !b->wpi && !xb) ? ks->box_rhs_held : nullptr;
+    k.fact_held = (b->use_box && !b->wpi && !xb) ? ks->box_fact_held : nullptr;
     if (b->use_box && !b->wpi && b->kb_plain && ks->kb_fact[xb])
     {
         k.fact = ks->kb_fact[xb]; k.rhs = ks->kb_rhs[xb]; k.faff = ks->kb_fwd_aff[xb]; k.fcorr = ks->kb_fwd_corr[xb];
         k.rhs_held = xb ? nullptr : ks->kb_rhs_held;
+        k.fact_held = xb ? nullptr : ks->kb_fact_held;
     }
     k.final_ = b->use_box ? ks->box_finalize : ks->finalize;
     return k;
@@ -1715,11 +1721,12 @@ static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, SubRole role, int i
  *
  * Held dynamics (ipm_kernels_box.hpp): the ROOT level zeroes GqpDev::tile_inv in front of its loop and behind it, lets its first
  * affine forward sweep count the lanes with stage-invariant [B A]' into it (GqpOpts::hold bit 1) and runs every sweep of its loop
- * with GqpOpts::hold bit 0.  The counters are read back behind that sweep and counted at the loop's next synchronisation
- * ("tiles_invariant").  From then on, if EVERY tile of the batch is held, both rhs-only launches of an iteration go to the entry
- * that holds the block too (IpmKernels::rhs_held, gqp::kh_backrhs; counted in "rhs_held_launches"); a mixed batch, the iteration that
- * detects and every launch outside this loop (sub-levels, tail, sensitivities, ric_alg 0) keep K.rhs, which fetches at every
- * stage.  Sub-levels never set either bit and their counters stay zero: nothing is copied by compact_into.  Every
+ * with GqpOpts::hold bit 0.  The counters are read back behind that sweep, an event is recorded behind the copy, and the host
+ * waits for that event -- not for the stream -- at the top of the next iteration and counts them ("tiles_invariant").  From then on,
+ * if EVERY tile of the batch is held, the factor launch and both rhs-only launches of an iteration go to the entries that hold the
+ * block too (IpmKernels::fact_held, gqp::kh_factor, "fact_held_launches"; IpmKernels::rhs_held, gqp::kh_backrhs,
+ * "rhs_held_launches"); a mixed batch, the iteration that detects and every launch outside this loop (sub-levels, tail,
+ * sensitivities, ric_alg 0) keep K.fact and K.rhs, which fetch at every stage.  Sub-levels never set either bit and their counters stay zero: nothing is copied by compact_into.  Every
  * other launch of these kernels (sensitivities, a later solve, the polish pass -- a root loop of its own, which detects again)
  * finds the counters at zero.
  */
@@ -1754,6 +1761,16 @@ static const int *side_map(ocp_qp_gpu_batch *b)
 #define GQP_HOLD_SYNC 0
 #endif
 
+/* host wait for ONE event (the host simulation copies synchronously: nothing to wait for) */
+static inline void gqp_event_wait(hipEvent_t e)
+{
+#if defined(__HIPCC__)
+    HIPCHK(hipEventSynchronize(e));
+#else
+    (void) e;
+#endif
+}
+
 static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hipStream_t s, int it)
 {
     const IpmKernels K = pick_kernels(b);
@@ -1775,6 +1792,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
     {
         root->n_tiles_invariant = 0;
         root->n_rhs_held_launches = 0;
+        root->n_fact_held_launches = 0;
         HIPCHK(hipMemsetAsync(D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
     }
     GqpOpts Oc = O; /* options of the corrector-sweep launches */
@@ -1810,14 +1828,30 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
     };
     for (;; it++)
     {
+        if (!detect && !counted)
+        {
+            /* the counters were copied back behind the detecting sweep of the iteration before: wait for THAT copy, not for the
+             * stream -- the rhs and corrector launches of that iteration are still queued behind it, the device does not idle --
+             * so that this factor launch can already be the held one */
+            gqp_event_wait(root->tiles_ev);
+            count_tiles();
+        }
+        /* the held entries (factor here, the rhs pair below) read no flag: one tile that must fetch keeps K.fact / K.rhs for the
+         * whole launch, and so does every launch in front of the count */
+        const bool all_held = hold && counted && root->n_tiles_invariant == (b->B + 63) / 64;
+        const bool fact_held = all_held && K.fact_held;
         if (b == root) prof.begin(1, s); /* per-class timing covers the root level only (full-batch launches) */
-        GQP_FACT_LAUNCH(b, K.fact, s, D, O, 0);
+        if (fact_held)
+        {
+            GQP_IPM_LAUNCH_SHM(b, K.fact_held, 0, s, D, O, 0);
+            root->n_fact_held_launches++;
+        }
+        else GQP_FACT_LAUNCH(b, K.fact, s, D, O, 0);
         if (b == root) prof.end(s);
         root->launches++;
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         const int nact = *b->h_nact;
-        if (!detect && !counted) count_tiles();
         if (root->print_level > 1) printf("acados_amd: ipm iter %d level size %d active %d\n", it, b->B, nact);
         if (nact <= 0 || it > O.iter_max) break;
         if (use_perm && nact >= 1 && 6 * nact <= 5 * b->w16_slots)
@@ -1862,6 +1896,8 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         if (detect)
         {
             HIPCHK(hipMemcpyAsync(b->h_ints, D.tile_inv, sizeof(int) * (size_t) (b->Bp / 64), hipMemcpyDeviceToHost, s));
+            if (!root->tiles_ev) HIPCHK(hipEventCreate(&root->tiles_ev)); /* once per batch */
+            HIPCHK(hipEventRecord(root->tiles_ev, s));
             detect = false;
 #if GQP_HOLD_SYNC
             HIPCHK(hipStreamSynchronize(s));
@@ -1871,7 +1907,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         /* the rhs pair of this iteration: the held entry when EVERY tile of the root batch was found stage-invariant -- it reads no
          * flag, so one tile that must fetch keeps K.rhs for the whole launch, and so does the iteration whose counters have not
          * arrived yet (the one that detects) */
-        const bool rhs_held = hold && K.rhs_held && counted && root->n_tiles_invariant == (b->B + 63) / 64;
+        const bool rhs_held = all_held && K.rhs_held;
         const kern_redo_t k_rhs = rhs_held ? K.rhs_held : K.rhs;
         if (b == root) prof.begin(3, s);
         GQP_SWEEP_LAUNCH(b, k_rhs, b->shmem, s, D, O, 0);
@@ -1947,10 +1983,11 @@ static void polish_pass(ocp_qp_gpu_batch *b, Prof &prof, hipStream_t s)
     b->O.tau_min = Oeff.tau_min; /* the barrier floor of the solve (derived from ITS tol_comp) */
     D.stat_inst = 0;             /* the statistics table keeps the solve's rows */
     const int keep_inv = b->n_tiles_invariant; /* ("tiles_invariant" speaks of the solve) */
-    const int keep_held = b->n_rhs_held_launches;
+    const int keep_held = b->n_rhs_held_launches, keep_fheld = b->n_fact_held_launches;
     run_ipm(b, b, prof, s, 0);
     b->n_tiles_invariant = keep_inv;
     b->n_rhs_held_launches += keep_held; /* ("rhs_held_launches": every launch of the held entry, this pass's included) */
+    b->n_fact_held_launches += keep_fheld;
     b->O = keep;
     D.stat_inst = keep_stat;
     hipLaunchKernelGGL(gqp::k_polish_restore, g64, blk, 0, s, D, Oeff, b->d_pol_status, b->d_pol_iter, b->d_pol_sc, b->d_pol_flag, b->d_pol_cnt + 1);
@@ -2666,6 +2703,7 @@ try
     if (!strcmp(f, "tail_switches")) return (double) b->n_tail_switches;
     if (!strcmp(f, "tiles_invariant")) return (double) b->n_tiles_invariant;
     if (!strcmp(f, "rhs_held_launches")) return (double) b->n_rhs_held_launches;
+    if (!strcmp(f, "fact_held_launches")) return (double) b->n_fact_held_launches;
     if (!strcmp(f, "single_launch_solves")) return (double) b->n_single_launch;
     if (!strcmp(f, "cond_N_active")) return b->pcond_state == 1 ? (double) b->child->N : (double) b->N;
     if (!strcmp(f, "tol_comp_soft_scale")) return b->tol_comp_soft_scale;

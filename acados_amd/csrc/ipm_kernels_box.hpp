@@ -18,7 +18,8 @@
  *     instead of a second pass over lam,t,dlam,dt;
  *   - fewer bytes again where the dynamics are the same at every stage: the two forward sweeps keep [B A]' in registers
  *     across the stages of a tile found stage-invariant (88 of the 153 / 228 doubles a C2 stage of these sweeps moves), and a
- *     batch whose tiles are ALL found so runs its rhs-only sweeps on kh_backrhs, which holds the block too (88 of 197), see
+ *     batch whose tiles are ALL found so runs its rhs-only sweeps on kh_backrhs, which holds the block too (88 of 197), and
+ *     its factor sweeps on kh_factor (A' and two rows of B' in LDS, one row in registers, W never stored: 88 of 241), see
  *     "HELD DYNAMICS" below; kb_factor (row chunks at its register ceiling) and kb_backrhs fetch the block as before.
  * Equality-flagged rows (idxe) are not IPM rows here; their multipliers are recovered from
  * stationarity in kb_finalize.
@@ -156,6 +157,12 @@ struct Acc
         return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff + (unsigned int) (j & 7) * 512u,
                                                                                   (unsigned int) (e0 + (j & ~7)) * bp8, 0));
     }
+    /* the same with the ordering token */
+    __device__ inline double ldjo(int e0, int j, int ord) const
+    {
+        return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff + (unsigned int) (j & 7) * 512u + (unsigned int) ord,
+                                                                                  (unsigned int) (e0 + (j & ~7)) * bp8, 0));
+    }
     __device__ inline void stj(int e0, int j, double v) const
     {
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(raw_t, v), rs, voff + (unsigned int) (j & 7) * 512u,
@@ -168,6 +175,7 @@ struct Acc
     double ldo(int e, int) const { return p[(size_t) e * bp]; }
     void st(int e, double v) const { p[(size_t) e * bp] = v; }
     double ldj(int e0, int j) const { return p[(size_t) (e0 + j) * bp]; }
+    double ldjo(int e0, int j, int) const { return p[(size_t) (e0 + j) * bp]; }
     void stj(int e0, int j, double v) const { p[(size_t) (e0 + j) * bp] = v; }
 #endif
 };
@@ -189,6 +197,54 @@ __device__ static inline Acc acc_at(GArr arr, size_t e0, int i)
     return a;
 }
 #define ACC(arr, e0) acc_at((arr), (size_t) (e0), i)
+
+/* the same in two steps: this wave's tile of an array, and an accessor at element offset e0 of it */
+__device__ static inline double *tile_ptr(GArr arr)
+{
+    return arr.p + (size_t) blockIdx.x * (size_t) arr.E * 64;
+}
+__device__ static inline Acc acc_tile(double *tile, size_t e0, int i)
+{
+    Acc a;
+    double *base = tile + e0 * 64;
+#if defined(__HIP_DEVICE_COMPILE__)
+    a.rs = __builtin_amdgcn_make_buffer_rsrc((void *) base, 0, 0xFFFFFFFFu, 0x00020000);
+    a.bp8 = 512u;
+    a.voff = (unsigned int) (i & 63) * 8u;
+#else
+    a.p = base + (i & 63);
+    a.bp = 64;
+#endif
+    return a;
+}
+
+/* a table of up to 64 wave-uniform pointers in ONE pair of vector registers, entry a in lane a (v_writelane / v_readlane address the
+ * lane whatever the execution mask says -- but the register copies the compiler makes do not: lanes 0 .. entries-1 must stay active
+ * as long as the table is read); what get() returns is a scalar value again */
+struct TileTab
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int lo = 0, hi = 0;
+    template <int A>
+    __device__ inline void put(double *p)
+    {
+        const uint64_t u = uni64((uint64_t) p);
+        asm("v_writelane_b32 %0, %1, %2" : "+v"(lo) : "s"((unsigned int) u), "n"(A)); /* (the lane as an immediate: one scalar operand) */
+        asm("v_writelane_b32 %0, %1, %2" : "+v"(hi) : "s"((unsigned int) (u >> 32)), "n"(A));
+    }
+    __device__ inline double *get(int a) const
+    {
+        const unsigned int l = (unsigned int) __builtin_amdgcn_readlane(lo, a), h = (unsigned int) __builtin_amdgcn_readlane(hi, a);
+        return (double *) (((uint64_t) h << 32) | l);
+    }
+#else
+    double *p[64];
+    template <int A>
+    __host__ __device__ void put(double *q) { p[A] = q; }
+    __host__ __device__ double *get(int a) const { return p[a]; }
+#endif
+};
+
 #define GATL_LD(arr, e) GATL(arr, e)
 
 /* Scheduling fence: hipcc's machine scheduler hoists every load of a straight-line stage body
@@ -203,8 +259,12 @@ __device__ static inline Acc acc_at(GArr arr, size_t e0, int i)
 #endif
 #if defined(__HIP_DEVICE_COMPILE__)
 #define GQP_OPAQUE(x) asm volatile("" : "+v"(x))
+#define GQP_OPAQUE_S(x) asm volatile("" : "+s"(x)) /* the same for a wave-uniform value: it stays in a scalar register */
+#define GQP_OPAQUE_D(x) asm("" : "+v"(x))          /* a double whose origin the compiler must not know; free to be scheduled */
 #else
 #define GQP_OPAQUE(x) do { } while (0)
+#define GQP_OPAQUE_S(x) do { } while (0)
+#define GQP_OPAQUE_D(x) do { } while (0)
 #endif
 
 /* x (an int living in a VGPR, always 0 or a lane index) becomes data-dependent on val */
@@ -270,7 +330,10 @@ __device__ static inline Acc acc_at(GArr arr, size_t e0, int i)
  * k = N .. 0, it fetches the block at the zero slot N (whose contents are 0) and at stage N-1, and the stages N-2 .. 0 reuse what
  * stage N-1 returned.  It reads no flag: run_ipm (gpu_batch.hip) launches it -- redo 0 and redo 1 alike -- only from the root loop,
  * once the detector's counters have been summed and EVERY tile of the batch is held; a mixed batch, the iteration that detects,
- * sub-levels, the tail, sensitivities and hold_dynamics 0 run kb_backrhs.  Scalar "rhs_held_launches" counts its launches. */
+ * sub-levels, the tail, sensitivities and hold_dynamics 0 run kb_backrhs.  Scalar "rhs_held_launches" counts its launches.
+ *   The factor sweep has the same two entries under the same condition: kb_factor, untouched, and kh_factor behind it (scalar
+ * "fact_held_launches").  The host waits for the read-back of the counters alone (an event behind that copy), so the factor
+ * launch of the second iteration is already the held one. */
 template <int NX, int NU, bool XBOX>
 constexpr bool kb_hold()
 {
@@ -286,6 +349,25 @@ __device__ static inline bool kb_tile_inv(const GqpDev &D, const GqpOpts &O)
 
 #define GQP_ROW_CHUNK 4  /* rows of [B A]' fetched per load phase in kb_factor */
 #define GQP_HROW_CHUNK 3 /* Hessian rows fetched per load phase in kb_factor */
+/* the arrays kh_factor touches (entries of its TileTab) */
+#define GQP_KH_ARRAYS(X) X(BAt) X(Lf) X(RSQ) X(bvec) X(dlam) X(dpi) X(dt) X(dux) X(dvec) X(lam) X(lf) X(pi) X(rb) X(rd) X(rg) X(rq) X(t) X(ux)
+#define GQP_KH_ENUM(name) KH_##name,
+enum { GQP_KH_ARRAYS(GQP_KH_ENUM) KH_COUNT };
+#undef GQP_KH_ENUM
+/* kh_factor, how its LDS reads are paced (the lane index of the reads is made to depend on an earlier result, as the load
+ * phases are on `ord`: without it hipcc issues all 80 reads of a column at once and holds their results in registers the
+ * kernel does not have).  LROWS: LDS rows of [B A]' read per such step; LAHEAD: the result the step waits for is the column
+ * entry this many rows back, i.e. how many rows of reads may be in flight.  1 / 2 is the first setting that built without
+ * scratch and spills; neither was timed against other settings. */
+#ifndef GQP_KH_LAHEAD
+#define GQP_KH_LAHEAD 2
+#endif
+#ifndef GQP_KH_LROWS
+#define GQP_KH_LROWS 1
+#endif
+#ifndef GQP_KH_BROWS_LDS
+#define GQP_KH_BROWS_LDS 2 /* kh_factor: rows of B' kept in LDS beside A' (the others: registers) */
+#endif
 
 /* row bookkeeping of variable j: exists?, compact row index (clamped to 0 when absent) */
 #define GQP_ROW(j, has, ib)                                                                    \
@@ -596,6 +678,365 @@ __global__ void __launch_bounds__(64) kb_factor(GqpDev D, GqpOpts O, int redo)
         D.status[i] = status;
         atomicSub(D.n_active, 1);
     }
+}
+
+/* The same sweep for a launch in which EVERY tile is held (see "HELD DYNAMICS"; the host's choice, run_ipm): [B A]' is fetched at the
+ * zero slot N and at stage N-1 only -- one branch on the scalar stage counter, no tile flag, no read of GqpDev::tile_inv -- and the
+ * stages N-2 .. 0 reuse it: the NX state rows (A') from LDS, [element][lane], in the 32 KB where kb_factor parks W, the NU input rows
+ * (B') from the 8 KB beside it (GQP_KH_BROWS_LDS = 2 rows) and from a loop-carried register array (the others).  W = [B A]' Lx+ is
+ * never stored: kb_factor forms M += W W' row by row and needs the rows c <= r again, here the sum runs column by column,
+ *     for q = 0 .. NX-1:   w_q[r] = sum_{p >= q} BAt[r][p] Lx[p][q];   S[r][c] += w_q[r] w_q[c];   mm[r] += w_q[r] w0[q]
+ * so that one column of W (n values) is all that exists at a time, and column q of Lx+ is dead once it is done.  S starts at 0.0 in
+ * the registers of M; the Hessian rows arrive behind it in the load phases of kb_factor, feed hv as there, and M = h + S with the
+ * diagonal's h = H + (reg_prim + gam) formed first.  Only the loop nest is interchanged: every scalar -- w (p ascending), S and mm
+ * (q ascending, one product per step), gt, rb, hv -- keeps its own chain of operations, and everything else is kb_factor<NX, NU,
+ * false> statement for statement, so every output is bit for bit what kb_factor writes -- with one place where the SOURCE being
+ * the same is not enough and the compiler's contraction has to be steered (the diagonal of S, see there).  What does differ from
+ * kb_factor: the padding lanes of the last tile ride along (below).  A kernel of its own for the reason kh_backrhs is one: the
+ * tiles that fetch must not pay. */
+template <int NX, int NU>
+__global__ void __launch_bounds__(64) kh_factor(GqpDev D, GqpOpts O, int redo)
+{
+    constexpr int n = NX + NU, NP = n * (n + 1) / 2, NPX = NX * (NX + 1) / 2, NB = NU;
+    static_assert(NX * NX * 64 * 8 <= 40 * 1024, "4 single-wave blocks per CU must fit");
+    const int Bp = D.Bp;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    /* The padding lanes of the last tile (i >= B; every array is allocated up to Bp) do not leave: they ride along as
+     * ghost lanes do.  The table of tile pointers below lives in the LANES of a vector register, and a register copy the compiler
+     * makes moves the active lanes only -- a lane that has left would take its entry with it.
+     * They load and store their (allocated) slots of every array: those hold zeros before the first held launch and the factor
+     * of a zero stage (sqrt(reg_prim) on the diagonal of Lf) after it; the other sweeps leave at i >= B and read none of it. */
+    const bool run = i < D.B && D.status[i] == GQP_RUNNING; /* (the statuses are allocated up to Bp too) */
+    if (!GQP_WAVE_ANY(run)) return;
+
+    /* A' of this tile ([element][lane], conflict-free 8-byte accesses): written at the two fetching stages, read at every stage
+     * through an opaque lane index so that hipcc does not forward the stored values into registers */
+    constexpr int NBL = GQP_KH_BROWS_LDS < NU ? GQP_KH_BROWS_LDS : NU; /* rows of B' that live in LDS too */
+    static_assert((NX + NBL) * NX * 64 * 8 <= 40 * 1024, "4 single-wave blocks per CU must fit");
+    __shared__ double Al[(NX + NBL) * NX * 64];
+#define GQP_KH_LDS(r) ((r) < NBL || (r) >= NU)                                  /* row r of [B A]' is in LDS */
+#define GQP_KH_SLOT(r) ((r) < NBL ? (r) : (r) >= NU ? NBL + (r) - NU : 0)       /* ... in this row of Al */
+#define GQP_KH_REG(r) ((r) >= NBL && (r) < NU ? (r) - NBL : 0)                  /* ... or in this row of Bt */
+    const int lane_w = threadIdx.x;
+    int lane_r = threadIdx.x;
+    GQP_OPAQUE(lane_r);
+    double Bt[(NU - NBL > 0 ? NU - NBL : 1) * NX]; /* the other rows of B', carried from stage to stage */
+    UNROLL for (int e = 0; e < (NU - NBL) * NX; e++) Bt[e] = 0.0;
+    /* this wave's tile of every array the sweep touches, one lane of `tiles` each: kept as scalar values across the stages, the 18
+     * pointers -- and hoisted out of the loop their buffer resources, four registers each -- overflow the scalar file, and the
+     * allocator parks them in spilled lanes anyway.  The resources are formed inside the stage, from a lane picked behind an opaque
+     * zero (KACC). */
+    TileTab tiles;
+#define GQP_KH_PUT(name) tiles.template put<KH_##name>(tile_ptr(D.name));
+    GQP_KH_ARRAYS(GQP_KH_PUT)
+#undef GQP_KH_PUT
+    tiles.template put<KH_COUNT>((double *) D.n_active); /* (and what only the epilogue needs: the counter, the statuses) */
+    tiles.template put<KH_COUNT + 1>((double *) D.status);
+    tiles.template put<KH_COUNT + 2>(D.stat);
+    tiles.template put<KH_COUNT + 3>((double *) (((uint64_t) (unsigned int) D.stat_rows << 32) | (unsigned int) D.stat_inst));
+    /* INVARIANT of every tiles.get(): lanes 0 .. KH_COUNT + 3 of the wave are active (no lane has returned, no divergent branch
+     * is open) -- true from here to the epilogue's reads, because no lane leaves before them and every branch of the stage body is
+     * on a wave-uniform value */
+#define KACC(name, e0) acc_tile(tiles.get(KH_##name + zs), (size_t) (e0), i)
+    double Lx[NPX], lx[NX];
+    UNROLL for (int e = 0; e < NPX; e++) Lx[e] = 0.0;
+    UNROLL for (int c = 0; c < NX; c++) lx[c] = 0.0;
+    double nrm_g = 0.0, nrm_b = 0.0, nrm_d = 0.0, nrm_m = 0.0, musum = 0.0, obj = 0.0;
+    int nact = 0;
+    double xn[NX], pin[NX]; /* x_{k+1}, pi_{k+1}: carried, see kb_factor */
+    UNROLL for (int c = 0; c < NX; c++) { xn[c] = 0.0; pin[c] = 0.0; }
+#if GQP_KB_FOLD
+    const double apd = run ? D.apend[i] : 0.0; /* folded update, see kb_factor */
+    const bool pend = apd != 0.0;
+#endif
+
+    for (int k = D.N; k >= 0; k--)
+    {
+        const StageU S = stage_u(D.st, k);
+        const uint64_t imask = S.bmask & ~S.emask;
+        const uint64_t am = GAT(D.amask, k);
+        const int nbg = S.nb;
+        int ord = 0; /* ordering token of the load phases, see kb_factor */
+        int zs = 0;  /* always zero, and opaque: see KACC */
+        GQP_OPAQUE_S(zs);
+
+        if (k >= D.N - 1)
+        {
+            const Acc aB = KACC(BAt, k * n * NX);
+            UNROLL for (int r = 0; r < n; r++)
+                UNROLL for (int c = 0; c < NX; c++)
+                {
+                    const double x = aB.ldj(0, r * NX + c);
+                    if (GQP_KH_LDS(r)) Al[(GQP_KH_SLOT(r) * NX + c) * 64 + lane_w] = x;
+                    else Bt[GQP_KH_REG(r) * NX + c] = x;
+                }
+        }
+
+        /* ---------------- phase 0 loads: what the dynamics rows need ---------------- */
+        double rb[NX], v[n], gt[n];
+        UNROLL for (int c = 0; c < NX; c++) rb[c] = KACC(bvec, 0).ldj(k * NX, c) - xn[c];
+        UNROLL for (int j = 0; j < n; j++) v[j] = KACC(ux, 0).ldj(k * n, j);
+#if GQP_KB_FOLD
+        {
+            double dv[n];
+            UNROLL for (int j = 0; j < n; j++) dv[j] = KACC(dux, 0).ldj(k * n, j);
+            UNROLL for (int j = 0; j < n; j++) v[j] = pend ? v[j] + apd * dv[j] : v[j];
+            UNROLL for (int j = 0; j < n; j++) KACC(ux, 0).stj(k * n, j, v[j]);
+        }
+#endif
+
+        /* ---------------- dynamics: rb += row*v_r, gt_r = row.pi+ (state rows two at a time: bounded LDS reads in flight) -------- */
+        int lr = lane_r;
+        UNROLL for (int r = 0; r < n; r++)
+        {
+            if (GQP_KH_LDS(r) && GQP_KH_SLOT(r) % GQP_KH_LROWS == 0) GQP_AFTER(lr, rb[0]);
+            double row[NX];
+            UNROLL for (int c = 0; c < NX; c++) row[c] = GQP_KH_LDS(r) ? Al[(GQP_KH_SLOT(r) * NX + c) * 64 + lr] : Bt[GQP_KH_REG(r) * NX + c];
+            double a = 0.0;
+            UNROLL for (int c = 0; c < NX; c++)
+            {
+                a += row[c] * pin[c];
+                rb[c] += row[c] * v[r];
+            }
+            gt[r] = a; /* BAt pi+ ; gradient and H v are added below */
+        }
+        /* w0 = Lx+' rb + lx+ (needs the final rb) */
+        double w0[NX];
+        UNROLL for (int c = 0; c < NX; c++)
+        {
+            double a = lx[c];
+            UNROLL for (int q = c; q < NX; q++) a += Lx[PK(q, c)] * rb[q];
+            w0[c] = a;
+        }
+
+        /* ---------------- box rows (need v only) ---------------- */
+        GQP_AFTER(ord, w0[0]);
+        double g[n], pik[NX];
+        UNROLL for (int j = 0; j < n; j++) g[j] = KACC(rq, 0).ldjo(k * n, j, ord);
+        UNROLL for (int c = 0; c < NX; c++) pik[c] = KACC(pi, 0).ldjo(k * NX, c, ord);
+#if GQP_KB_FOLD
+        if (k > 0) /* (slot 0 of pi is zero by convention and takes no step) */
+        {
+            double dp[NX];
+            UNROLL for (int c = 0; c < NX; c++) dp[c] = KACC(dpi, 0).ldjo(k * NX, c, ord);
+            UNROLL for (int c = 0; c < NX; c++) pik[c] = pend ? pik[c] + apd * dp[c] : pik[c];
+            UNROLL for (int c = 0; c < NX; c++) KACC(pi, 0).stj(k * NX, c, pik[c]);
+        }
+#endif
+        double rdl[NB], rdu[NB], gadd[NB], gam[NB];
+        UNROLL for (int j = 0; j < NB; j++)
+        {
+            GQP_ROW(j, has, ib);
+            const int el = S.o_ct + ib, eu = el + nbg;
+            const double lbv = KACC(dvec, 0).ldo(el, ord), ubv = KACC(dvec, 0).ldo(eu, ord);
+#if GQP_KB_FOLD
+            double laml = KACC(lam, 0).ldo(el, ord), lamu = KACC(lam, 0).ldo(eu, ord);
+            double tl = KACC(t, 0).ldo(el, ord), tu = KACC(t, 0).ldo(eu, ord);
+            const bool al = has && ((am >> ib) & 1), au = has && ((am >> (nbg + ib)) & 1);
+            {
+                const double dll = KACC(dlam, 0).ldo(el, ord), dlu = KACC(dlam, 0).ldo(eu, ord);
+                const double dtl = KACC(dt, 0).ldo(el, ord), dtu = KACC(dt, 0).ldo(eu, ord);
+                const double nll = laml + apd * dll, nlu = lamu + apd * dlu, ntl = tl + apd * dtl, ntu = tu + apd * dtu;
+                laml = (pend && al) ? (nll < O.lam_min ? O.lam_min : nll) : laml;
+                lamu = (pend && au) ? (nlu < O.lam_min ? O.lam_min : nlu) : lamu;
+                tl = (pend && al) ? (ntl < O.t_min ? O.t_min : ntl) : tl;
+                tu = (pend && au) ? (ntu < O.t_min ? O.t_min : ntu) : tu;
+                if (has)
+                {
+                    KACC(lam, 0).st(el, laml); KACC(lam, 0).st(eu, lamu);
+                    KACC(t, 0).st(el, tl); KACC(t, 0).st(eu, tu);
+                }
+            }
+#else
+            const double laml = KACC(lam, 0).ldo(el, ord), lamu = KACC(lam, 0).ldo(eu, ord);
+            const double tl = KACC(t, 0).ldo(el, ord), tu = KACC(t, 0).ldo(eu, ord);
+            const bool al = has && ((am >> ib) & 1), au = has && ((am >> (nbg + ib)) & 1);
+#endif
+            const double ll = al ? laml : 0.0, lu = au ? lamu : 0.0;
+            const double ttl = al ? tl : 1.0, ttu = au ? tu : 1.0;
+            rdl[j] = al ? v[j] - lbv - ttl : 0.0;
+            rdu[j] = au ? ubv - v[j] - ttu : 0.0;
+            const double rml = al ? ll * ttl - O.tau_min : 0.0, rmu = au ? lu * ttu - O.tau_min : 0.0;
+            nacc(nrm_d, rdl[j]); nacc(nrm_d, rdu[j]); nacc(nrm_m, rml); nacc(nrm_m, rmu);
+            musum += ll * ttl + lu * ttu;
+            nact += (int) al + (int) au;
+            gt[j] -= ll - lu;
+            const double itl = frcp(ttl), itu = frcp(ttu);
+            gam[j] = ll * itl + lu * itu;
+            gadd[j] = (rml + ll * rdl[j]) * itl - (rmu + lu * rdu[j]) * itu;
+        }
+
+        /* ---------------- S = W W' and W w0, one column of W at a time ---------------- */
+        double M[NP], hv[n], mm[n];
+        UNROLL for (int e = 0; e < NP; e++) M[e] = 0.0;
+        UNROLL for (int r = 0; r < n; r++) mm[r] = 0.0;
+        GQP_AFTER(lr, gt[0]);
+        UNROLL for (int q = 0; q < NX; q++)
+        {
+            double w[n];
+            UNROLL for (int r = 0; r < n; r++)
+            {
+                if (GQP_KH_LDS(r) && GQP_KH_SLOT(r) % GQP_KH_LROWS == 0 && r >= GQP_KH_LAHEAD) GQP_AFTER(lr, w[r - GQP_KH_LAHEAD]);
+                double a = 0.0;
+                UNROLL for (int p = q; p < NX; p++)
+                    a += (GQP_KH_LDS(r) ? Al[(GQP_KH_SLOT(r) * NX + p) * 64 + lr] : Bt[GQP_KH_REG(r) * NX + p]) * Lx[PK(p, q)];
+                w[r] = a;
+            }
+            UNROLL for (int r = 0; r < n; r++)
+            {
+                mm[r] += w[r] * w0[q];
+                UNROLL for (int c = 0; c < r; c++) M[PK(r, c)] += w[r] * w[c];
+                /* The diagonal.  With contraction on, hipcc knows that x * x is no -0.0, drops the `0.0 +` in front of the first
+                 * square and is then free to fuse EITHER of the first two squares into the sum -- and takes the other one, which
+                 * rounds differently.  kb_factor gives it that freedom in the rows whose two factors are one value (the rows of
+                 * Wu, and the first two state rows, read once under one lane token) and not in the others (row c read again
+                 * under a new token): the second factor is hidden in exactly those rows here, so that both entries contract
+                 * alike (the device tier of tests/test_hold_factor.py is what holds this in place). */
+                double wd = w[r];
+                if (r >= NU + 2) GQP_OPAQUE_D(wd);
+                M[PK(r, r)] += w[r] * wd;
+            }
+        }
+        UNROLL for (int r = 0; r < n; r++) mm[r] = mm[r] + (r < NB ? gadd[r < NB ? r : 0] : 0.0);
+
+        /* ---------------- Hessian rows in load phases: H v, M = H~ + S ---------------- */
+        UNROLL for (int r = 0; r < n; r++) hv[r] = 0.0;
+        const Acc aRSQ = KACC(RSQ, k * NP);
+        double H[GQP_HROW_CHUNK * n];
+        UNROLL for (int r = 0; r < n; r++)
+        {
+            if (r % GQP_HROW_CHUNK == 0)
+            {
+                /* next chunk of Hessian rows; ordered after S (first chunk) / after the previous chunk's last sum */
+                GQP_AFTER(ord, M[r > 0 ? PK(r - 1, r - 1) : NP - 1]);
+                UNROLL for (int r2 = r; r2 < n && r2 < r + GQP_HROW_CHUNK; r2++)
+                    UNROLL for (int c = 0; c <= r2; c++) H[(r2 % GQP_HROW_CHUNK) * n + c] = aRSQ.ldjo(0, PK(r2, c), ord);
+            }
+            double *const h = H + (r % GQP_HROW_CHUNK) * n;
+            UNROLL for (int c = 0; c < r; c++)
+            {
+                hv[r] += h[c] * v[c];
+                hv[c] += h[c] * v[r];
+            }
+            hv[r] += h[r] * v[r];
+            h[r] += O.reg_prim + (r < NB ? gam[r < NB ? r : 0] : 0.0);
+            UNROLL for (int c = 0; c <= r; c++) M[PK(r, c)] = h[c] + M[PK(r, c)];
+        }
+        UNROLL for (int r = 0; r < n; r++)
+        {
+            obj += (0.5 * hv[r] + g[r]) * v[r];
+            gt[r] += hv[r] + g[r];
+        }
+        UNROLL for (int c = 0; c < NX; c++) gt[NU + c] -= pik[c];
+        /* residual norms; fixed variables carry no residual */
+        UNROLL for (int j = 0; j < n; j++)
+        {
+            if ((S.emask >> j) & 1) gt[j] = 0.0;
+            nacc(nrm_g, gt[j]);
+        }
+        UNROLL for (int c = 0; c < NX; c++) nacc(nrm_b, rb[c]);
+        UNROLL for (int j = 0; j < n; j++) KACC(rg, 0).stj(k * n, j, gt[j]);
+        UNROLL for (int c = 0; c < NX; c++) KACC(rb, 0).stj(k * NX, c, rb[c]);
+        /* m = stationarity residual + condensed inequality terms + W w0 */
+        UNROLL for (int j = 0; j < n; j++) gt[j] += mm[j];
+        /* fixed variables: unit row/column, zero rhs (select, no branch) */
+        UNROLL for (int r = 0; r < n; r++)
+        {
+            const bool fr = (S.emask >> r) & 1;
+            if (fr) gt[r] = 0.0;
+            UNROLL for (int c = 0; c <= r; c++)
+            {
+                const bool fc = (S.emask >> c) & 1;
+                M[PK(r, c)] = (fr || fc) ? (r == c ? 1.0 : 0.0) : M[PK(r, c)];
+            }
+        }
+        /* ---------------- Cholesky (inverse diagonal kept in registers) ---------------- */
+        double invd[n];
+        UNROLL for (int jc = 0; jc < n; jc++)
+        {
+            const double d = M[PK(jc, jc)];
+            const bool pos = d > 0.0;
+            const double r0 = frsqrt(pos ? d : 1.0); /* unconditional: no branch around v_rsq */
+            const double inv = pos ? r0 : 0.0;
+            invd[jc] = inv;
+            M[PK(jc, jc)] = pos ? d * inv : 0.0;
+            UNROLL for (int r = jc + 1; r < n; r++) M[PK(r, jc)] *= inv;
+            UNROLL for (int c = jc + 1; c < n; c++)
+                UNROLL for (int r = c; r < n; r++) M[PK(r, c)] -= M[PK(r, jc)] * M[PK(c, jc)];
+        }
+        UNROLL for (int e = 0; e < NP; e++) KACC(Lf, 0).stj(k * NP, e, M[e]);
+        UNROLL for (int r = 0; r < n; r++)
+        {
+            double a = gt[r];
+            UNROLL for (int c = 0; c < r; c++) a -= M[PK(r, c)] * gt[c];
+            gt[r] = a * invd[r];
+            KACC(lf, 0).stj(k * n, r, gt[r]);
+        }
+        UNROLL for (int r = 0; r < NX; r++)
+        {
+            lx[r] = gt[NU + r];
+            UNROLL for (int c = 0; c <= r; c++) Lx[PK(r, c)] = M[PK(NU + r, NU + c)];
+        }
+        UNROLL for (int c = 0; c < NX; c++) { xn[c] = v[NU + c]; pin[c] = pik[c]; }
+        /* rd of the existing rows (rm = lam*t - tau is recomputed by the consumers) */
+        UNROLL for (int j = 0; j < NB; j++)
+        {
+            GQP_ROW(j, has, ib);
+            if (has)
+            {
+                KACC(rd, 0).st(S.o_ct + ib, rdl[j]);
+                KACC(rd, 0).st(S.o_ct + nbg + ib, rdu[j]);
+            }
+        }
+    }
+
+    /* every entry the epilogue needs is taken out of the table HERE, while all lanes are still active */
+    int *const status_p = (int *) tiles.get(KH_COUNT + 1);
+    int *const n_active_p = (int *) tiles.get(KH_COUNT);
+    double *const stat_p = tiles.get(KH_COUNT + 2);
+    const uint64_t stat_dims = (uint64_t) tiles.get(KH_COUNT + 3);
+    if (status_p[i] != GQP_RUNNING) return; /* (`run` again: nothing has written the status since; a padding lane's is 0) */
+#if GQP_KB_FOLD
+    D.apend[i] = 0.0; /* applied */
+#endif
+    const double mu = nact > 0 ? musum / nact : 0.0;
+    D.mu[i] = mu;
+    D.obj[i] = obj;
+    D.res[0 * Bp + i] = nrm_g; D.res[1 * Bp + i] = nrm_b; D.res[2 * Bp + i] = nrm_d; D.res[3 * Bp + i] = nrm_m;
+    const int it = D.iter[i];
+    const int stat_inst = (int) (unsigned int) stat_dims, stat_rows = (int) (unsigned int) (stat_dims >> 32);
+    if (i < stat_inst && it < stat_rows)
+    {
+        double *st = stat_p + (size_t) it * GQP_STAT_COLS * stat_inst + i;
+        st[6 * stat_inst] = mu;
+        st[7 * stat_inst] = nrm_g; st[8 * stat_inst] = nrm_b; st[9 * stat_inst] = nrm_d; st[10 * stat_inst] = nrm_m;
+        st[12 * stat_inst] = obj;
+    }
+    int status = GQP_RUNNING;
+    const bool bad = nrm_g != nrm_g || nrm_b != nrm_b || nrm_d != nrm_d || nrm_m != nrm_m || mu != mu;
+    if (bad) status = 1;
+    else if (nrm_g <= O.tol_stat && nrm_b <= O.tol_eq && nrm_d <= O.tol_ineq && nrm_m <= O.tol_comp) status = 0;
+    else if (it >= O.iter_max) status = 2;
+    else if (dabs(D.alpha[i]) <= O.alpha_min) status = 3;
+    if (status != GQP_RUNNING)
+    {
+        status_p[i] = status;
+        atomicSub(n_active_p, 1);
+    }
+}
+#undef KACC
+#undef GQP_KH_LDS
+#undef GQP_KH_SLOT
+#undef GQP_KH_REG
+
+/* the held entry of a shape, null where the block does not fit beside the stage (kb_hold) -- and for every shape but <8, 3>:
+ * <4, 4> and <4, 1> build without scratch or spills, but bit-identity with kb_factor rests on how hipcc contracts BOTH kernels (the
+ * diagonal of S above), and only <8, 3> has a device test that compares them (tests/test_hold_factor.py) */
+template <int NX, int NU>
+constexpr auto kh_factor_for() -> void (*)(GqpDev, GqpOpts, int)
+{
+    if constexpr (kb_hold<NX, NU, false>() && NX == 8 && NU == 3) return kh_factor<NX, NU>;
+    else return nullptr;
 }
 
 /* ------------------------------------------------------- rhs-only backward */

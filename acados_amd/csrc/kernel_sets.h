@@ -30,6 +30,9 @@ struct KernelSet
     /* the rhs-only sweep with [B A]' held across the stages (gqp::kh_backrhs, no XBOX), for launches in which every tile is held:
      * beside box_rhs[0] (null where the small-block kernels serve the shape) and beside kb_rhs[0]; null where not instantiated */
     kern_redo_t box_rhs_held, kb_rhs_held;
+    /* the factor sweep of such launches (gqp::kh_factor: A' and two rows of B' in LDS, the third in registers, W never stored), in the
+     * same places; instantiated for <8, 3> only (kh_factor_for) */
+    kern_redo_t box_fact_held, kb_fact_held;
 };
 
 #define GQP_KSET(NX, NU, NG, NS)                                                               \
@@ -45,7 +48,8 @@ struct KernelSet
      {gqp::kb_backrhs<NX, NU, false>, gqp::kb_backrhs<NX, NU, true>},                          \
      {gqp::kb_forward<NX, NU, false, false>, gqp::kb_forward<NX, NU, true, false>},            \
      {gqp::kb_forward<NX, NU, false, true>, gqp::kb_forward<NX, NU, true, true>},              \
-     gqp::KbSmall<NX, NU>::value ? nullptr : gqp::kh_backrhs_for<NX, NU>(), gqp::kh_backrhs_for<NX, NU>()}
+     gqp::KbSmall<NX, NU>::value ? nullptr : gqp::kh_backrhs_for<NX, NU>(), gqp::kh_backrhs_for<NX, NU>(),                           \
+     gqp::KbSmall<NX, NU>::value ? nullptr : gqp::kh_factor_for<NX, NU>(), gqp::kh_factor_for<NX, NU>()}
 
 /* partial condensing: parent shape (NX, NU), blocks of at most BSMAX stages -> child shape
  * (NX, BSMAX*NU); kernels in pcond_kernels.hpp */
