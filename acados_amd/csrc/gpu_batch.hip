@@ -154,6 +154,36 @@ struct BulkMap
     gqp::GArrTable T;
 };
 
+/* Held dynamics of the one-instance-per-lane box sweeps (ipm_kernels_box.hpp), the host's side, owned by the root batch.  One
+ * root loop (run_ipm; the polish pass is a root loop of its own) goes DETECTING -> AWAITING -> COUNTED: begin() zeroes
+ * GqpDev::tile_inv; the first affine forward sweep runs with bits(true) and counts the lanes with stage-invariant [B A]' into it;
+ * after_detect() copies the counters back and records an event behind the copy; before_factor(), at the top of the next iteration,
+ * waits for that event -- not for the stream -- and counts the full tiles; from then on all_held() says whether a launch may take
+ * the held entries; end() zeroes tile_inv again, so every other launch of these kernels (sub-levels, sensitivities, a later solve)
+ * finds the counters at zero.  Methods: in front of run_ipm. */
+struct HeldDynamics
+{
+    /* the last solve: scalars "tiles_invariant" (of the solve's own loop), "fact_held_launches" / "rhs_held_launches" (launches of
+     * IpmKernels::fact_held / rhs_held, the polish pass's included); reset by ocp_qp_gpu_batch_solve */
+    int tiles_invariant = 0, fact_launches = 0, rhs_launches = 0;
+    hipEvent_t ev = nullptr; /* recorded behind the read-back of the counters */
+    /* the root loop that runs */
+    ocp_qp_gpu_batch *b = nullptr; /* null: a sub-level's record, which does nothing */
+    bool enabled = false;          /* option hold_dynamics on a one-instance-per-lane box batch */
+    bool polish = false;           /* the loop of the polish pass: its count stays its own */
+    enum { DETECTING, AWAITING, COUNTED } state = COUNTED;
+    int tiles = 0;                 /* full tiles this loop counted */
+
+    void begin(ocp_qp_gpu_batch *root, hipStream_t s, bool polish_loop);
+    /* GqpOpts::hold of a launch of this loop: bit 0 tiles with a full counter hold; bit 1 (the affine sweep while DETECTING) count */
+    int bits(bool affine_sweep = false) const { return !enabled ? 0 : (affine_sweep && state == DETECTING) ? 3 : 1; }
+    void after_detect(hipStream_t s);
+    void before_factor();
+    void count();
+    bool all_held() const;
+    void end(hipStream_t s);
+};
+
 struct ocp_qp_gpu_batch
 {
     int B = 0, Bp = 0, N = 0, device = 0;
@@ -264,10 +294,7 @@ struct ocp_qp_gpu_batch
     int n_tail_switches = 0;
     /* held dynamics of the one-instance-per-lane box sweeps (ipm_kernels_box.hpp; run_ipm) */
     int hold_dynamics = 1;               /* option: 1 = tiles whose [B A]' is found stage-invariant keep it in registers, 0 = never */
-    int n_tiles_invariant = 0;           /* tiles found so by the last solve */
-    int n_rhs_held_launches = 0;         /* launches of the held rhs entry (IpmKernels::rhs_held) in the last solve */
-    int n_fact_held_launches = 0;        /* launches of the held factor entry (IpmKernels::fact_held) in the last solve */
-    hipEvent_t tiles_ev = nullptr;       /* recorded behind the read-back of the held-dynamics counters (run_ipm) */
+    HeldDynamics held;                   /* the protocol of the root loop and what the last solve counted */
     /* solution sensitivities / factor at the solution */
     bool factor_stale = false;           /* the last solve finished instances on a sub-level: Lf of the root is not theirs */
     bool sens_open = false;              /* seeds are being collected (rg, rb, rd hold seeds, not residuals) */
@@ -387,7 +414,7 @@ KernelSet wpi_ric0_set(int wx, int wu, int mg, int ms)
     const kern_redo_t fcor = gen ? gqp::kw_fwd<true, true, 0, 0, true> : gqp::kw_fwd<true, false, 0, 0, true>;
     const kern_opts_t init = gen ? gqp::kw_init<true> : gqp::kw_init<false>;
     const kern_plain_t fin = gen ? gqp::kw_finalize<true> : gqp::kw_finalize<false>;
-    return KernelSet{wx, wu, mg, ms, init, fact, rhs, faff, fcor, fin, {fact, fact}, {rhs, rhs}, {faff, faff}, {fcor, fcor}, fin};
+    return KernelSet{wx, wu, mg, ms, init, fact, rhs, faff, fcor, fin, {{fact, fact}, {rhs, rhs}, {faff, faff}, {fcor, fcor}}, fin};
 }
 
 /* dynamic LDS above the default limit: raise it for the four sweep kernels of the batch's own set */
@@ -1076,7 +1103,7 @@ static ocp_qp_gpu_batch *batch_create_shape(int N, const int *nx, const int *nu,
             const kern_opts_t init = gen ? gqp::kw_init<true> : gqp::kw_init<false>;
             const kern_plain_t fin = gen ? gqp::kw_finalize<true> : gqp::kw_finalize<false>;
             b->own_ks = KernelSet{wx, wu, mg, ms, init, fact, rhs, faff, fcor, fin,
-                                  {fact, fact}, {rhs, rhs}, {faff, faff}, {fcor, fcor}, fin};
+                                  {{fact, fact}, {rhs, rhs}, {faff, faff}, {fcor, fcor}}, fin};
             b->ks = &b->own_ks;
             b->wpi = 1;
             b->aos = 1;
@@ -1094,8 +1121,8 @@ static ocp_qp_gpu_batch *batch_create_shape(int N, const int *nx, const int *nu,
                 b->own_ks.back_fact = kf; b->own_ks.back_rhs = kr; b->own_ks.fwd_aff = ka; b->own_ks.fwd_corr = kc;
                 for (int q = 0; q < 2; q++)
                 {
-                    b->own_ks.box_fact[q] = kf; b->own_ks.box_rhs[q] = kr;
-                    b->own_ks.box_fwd_aff[q] = ka; b->own_ks.box_fwd_corr[q] = kc;
+                    b->own_ks.box.fact[q] = kf; b->own_ks.box.rhs[q] = kr;
+                    b->own_ks.box.fwd_aff[q] = ka; b->own_ks.box.fwd_corr[q] = kc;
                 }
                 b->w16 = 1;
                 b->w16_slots = n_batch;
@@ -1152,7 +1179,7 @@ try
     (void) hipEventDestroy(b->ev0);
     (void) hipEventDestroy(b->ev1);
     if (b->chunks_ev) (void) hipEventDestroy(b->chunks_ev);
-    if (b->tiles_ev) (void) hipEventDestroy(b->tiles_ev);
+    if (b->held.ev) (void) hipEventDestroy(b->held.ev);
     for (hipEvent_t e : b->prof_ev) (void) hipEventDestroy(e);
     (void) hipStreamDestroy(b->stream);
     if (b->child) ocp_qp_gpu_batch_destroy(b->child);
@@ -1632,53 +1659,61 @@ static int pcond_solve(ocp_qp_gpu_batch *b, int mode = 3)
 }
 
 /* ---- the IPM launch loop of one level (root batch or compaction sub-batch) ---- */
+extern "C++" { /* (templates among them: the surrounding block has C linkage) */
+/* a sweep kernel of one level with the dynamic LDS bytes it takes in that level's family (the one-instance-per-lane family: none) */
+struct Sweep
+{
+    kern_redo_t fn;
+    size_t shm;
+};
 struct IpmKernels
 {
-    kern_redo_t fact, rhs, faff, fcorr;
-    kern_redo_t rhs_held; /* K.rhs with [B A]' held across the stages, for a launch whose tiles are all held; null: there is none */
-    kern_redo_t fact_held; /* K.fact likewise (static LDS of its own, none of shmem_fact) */
+    Sweep fact, rhs, faff, fcorr;
+    Sweep fact_held, rhs_held; /* fact / rhs with [B A]' held across the stages, for a launch whose tiles are all held (static LDS of
+                                * their own); fn null: there is none */
     kern_plain_t final_;
 };
 
-/* launch geometry of the IPM kernels of one level: 64 instances per single-wave block (one instance per
- * lane) or one single-wave block per instance with the stage matrices in dynamic LDS (wpi) */
-#define GQP_IPM_LAUNCH_SHM(b, kern, shm, s, ...)                                                              \
-    do {                                                                                                      \
-        if ((b)->wpi) GQP_LAUNCH_COOP(kern, dim3((b)->B), dim3(64), shm, s, __VA_ARGS__);                     \
-        else hipLaunchKernelGGL(kern, dim3(((b)->B + 63) / 64), dim3(64), 0, s, __VA_ARGS__);                 \
-    } while (0)
-#define GQP_IPM_LAUNCH(b, kern, s, ...) GQP_IPM_LAUNCH_SHM(b, kern, (b)->shmem, s, __VA_ARGS__)
-/* the four sweeps: 16-lanes-per-instance batches pack 4 instances into one 64-lane workgroup */
-#define GQP_SWEEP_LAUNCH(b, kern, shm, s, ...)                                                                \
-    do {                                                                                                      \
-        if ((b)->w16) GQP_LAUNCH_COOP(kern, dim3(((b)->w16_slots + 3) / 4), dim3(64), (b)->w16_shmem, s, __VA_ARGS__);  \
-        else GQP_IPM_LAUNCH_SHM(b, kern, shm, s, __VA_ARGS__);                                                \
-    } while (0)
-
-/* the factor sweep: its own LDS tile in the sixteen-lanes families */
-#define GQP_FACT_LAUNCH(b, kern, s, ...)                                                                      \
-    do {                                                                                                      \
-        if ((b)->w16) GQP_LAUNCH_COOP(kern, dim3(((b)->w16_slots + 3) / 4), dim3(64), (b)->w16_shmem_fact, s, __VA_ARGS__); \
-        else GQP_IPM_LAUNCH_SHM(b, kern, (b)->shmem_fact, s, __VA_ARGS__);                                    \
-    } while (0)
+/* One launch of a kernel of level b.  Grid and launch form come from the family, here and nowhere else: the four sweeps of a
+ * sixteen-lanes batch pack 4 row slots into a 64-lane workgroup (w16_slots is read NOW: run_ipm shrinks it when the permutation comes
+ * on); the wave-per-instance families take one single-wave workgroup per instance, stage matrices in dynamic LDS; one instance per
+ * lane is a plain launch of 64 instances per single-wave block without dynamic LDS. */
+template <class Kern, class... Args>
+static void launch_level(const ocp_qp_gpu_batch *b, Kern fn, size_t shm, bool sweep, hipStream_t s, const Args &...args)
+{
+    if (sweep && b->w16) GQP_LAUNCH_COOP(fn, dim3((b->w16_slots + 3) / 4), dim3(64), shm, s, args...);
+    else if (b->wpi) GQP_LAUNCH_COOP(fn, dim3(b->B), dim3(64), shm, s, args...);
+    else hipLaunchKernelGGL(fn, dim3((b->B + 63) / 64), dim3(64), 0, s, args...);
+}
+static void launch_sweep(const ocp_qp_gpu_batch *b, const Sweep &k, hipStream_t s, const GqpDev &D, const GqpOpts &O, int redo)
+{
+    launch_level(b, k.fn, k.shm, true, s, D, O, redo);
+}
+/* init and finalize: one block per instance / per 64 instances in every family, the LDS bytes of the rhs sweep */
+template <class Kern, class... Args>
+static void launch_whole(const ocp_qp_gpu_batch *b, Kern fn, hipStream_t s, const Args &...args)
+{
+    launch_level(b, fn, b->shmem, false, s, args...);
+}
 
 static IpmKernels pick_kernels(const ocp_qp_gpu_batch *b)
 {
     const KernelSet *ks = b->ks;
     const int xb = b->xbox;
+    const bool lane_box = b->use_box && !b->wpi;
+    /* the family's box sweeps: the serving ones, or the ipm_kernels_box.hpp kernels where the batch asks for them */
+    const BoxSweeps &bx = (lane_box && b->kb_plain && ks->kb.fact[xb]) ? ks->kb : ks->box;
+    const size_t lds_fact = b->w16 ? b->w16_shmem_fact : b->shmem_fact, lds_rhs = b->w16 ? b->w16_shmem : b->shmem;
+    const size_t lds_fwd = b->w16 ? b->w16_shmem : b->shmem_fwd;
     IpmKernels k;
-    k.fact = b->use_box ? ks->box_fact[xb] : ks->back_fact;
-    k.rhs = b->use_box ? ks->box_rhs[xb] : ks->back_rhs;
-    k.faff = b->use_box ? ks->box_fwd_aff[xb] : ks->fwd_aff;
-    k.fcorr = b->use_box ? ks->box_fwd_corr[xb] : ks->fwd_corr;
-    k.rhs_held = (b->use_box && !b->wpi && !xb) ? ks->box_rhs_held : nullptr;
-    k.fact_held = (b->use_box && !b->wpi && !xb) ? ks->box_fact_held : nullptr;
-    if (b->use_box && !b->wpi && b->kb_plain && ks->kb_fact[xb])
-    {
-        k.fact = ks->kb_fact[xb]; k.rhs = ks->kb_rhs[xb]; k.faff = ks->kb_fwd_aff[xb]; k.fcorr = ks->kb_fwd_corr[xb];
-        k.rhs_held = xb ? nullptr : ks->kb_rhs_held;
-        k.fact_held = xb ? nullptr : ks->kb_fact_held;
-    }
+    k.fact = {b->use_box ? bx.fact[xb] : ks->back_fact, lds_fact};
+    k.rhs = {b->use_box ? bx.rhs[xb] : ks->back_rhs, lds_rhs};
+    k.faff = {b->use_box ? bx.fwd_aff[xb] : ks->fwd_aff, lds_fwd};
+    k.fcorr = {b->use_box ? bx.fwd_corr[xb] : ks->fwd_corr, lds_fwd};
+    /* held entries: one instance per lane, box rows on the controls only */
+    const bool held = lane_box && !xb;
+    k.fact_held = {held ? bx.fact_held : nullptr, 0};
+    k.rhs_held = {held ? bx.rhs_held : nullptr, 0};
     k.final_ = b->use_box ? ks->box_finalize : ks->finalize;
     return k;
 }
@@ -1688,28 +1723,35 @@ struct Prof
 {
     ocp_qp_gpu_batch *root;
     size_t used = 0;
-    void begin(int cls, hipStream_t s)
+    /* launch() bracketed by an event pair of class cls -- where `on`: the root level only (full-batch launches) */
+    template <class F>
+    void timed(int cls, hipStream_t s, bool on, F &&launch)
     {
-        if (!root->profile) return;
-        if (used + 2 > root->prof_ev.size())
+        on = on && root->profile;
+        if (on)
         {
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-            root->prof_ev.push_back(e0); root->prof_ev.push_back(e1);
+            if (used + 2 > root->prof_ev.size())
+            {
+                hipEvent_t e0, e1;
+                HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+                root->prof_ev.push_back(e0); root->prof_ev.push_back(e1);
+            }
+            root->prof_cls.push_back(cls);
+            HIPCHK(hipEventRecord(root->prof_ev[used], s));
         }
-        root->prof_cls.push_back(cls);
-        HIPCHK(hipEventRecord(root->prof_ev[used], s));
-    }
-    void end(hipStream_t s)
-    {
-        if (!root->profile) return;
-        HIPCHK(hipEventRecord(root->prof_ev[used + 1], s));
-        used += 2;
+        launch();
+        if (on)
+        {
+            HIPCHK(hipEventRecord(root->prof_ev[used + 1], s));
+            used += 2;
+        }
     }
 };
+} /* extern "C++" */
 
 static ocp_qp_gpu_batch *compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, hipStream_t s, SubRole role);
 static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, SubRole role, int it0);
+static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hipStream_t s, int it, bool polish = false);
 
 /*
  * One level of the IPM loop.  After the factor kernel of every iteration the host reads the
@@ -1719,16 +1761,12 @@ static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, SubRole role, int i
  * copied into a dense sub-batch, the loop continues there (recursively), and the results are
  * scattered back.  Per-instance arithmetic is unchanged, so results are bit-identical.
  *
- * Held dynamics (ipm_kernels_box.hpp): the ROOT level zeroes GqpDev::tile_inv in front of its loop and behind it, lets its first
- * affine forward sweep count the lanes with stage-invariant [B A]' into it (GqpOpts::hold bit 1) and runs every sweep of its loop
- * with GqpOpts::hold bit 0.  The counters are read back behind that sweep, an event is recorded behind the copy, and the host
- * waits for that event -- not for the stream -- at the top of the next iteration and counts them ("tiles_invariant").  From then on,
- * if EVERY tile of the batch is held, the factor launch and both rhs-only launches of an iteration go to the entries that hold the
- * block too (IpmKernels::fact_held, gqp::kh_factor, "fact_held_launches"; IpmKernels::rhs_held, gqp::kh_backrhs,
- * "rhs_held_launches"); a mixed batch, the iteration that detects and every launch outside this loop (sub-levels, tail,
- * sensitivities, ric_alg 0) keep K.fact and K.rhs, which fetch at every stage.  Sub-levels never set either bit and their counters stay zero: nothing is copied by compact_into.  Every
- * other launch of these kernels (sensitivities, a later solve, the polish pass -- a root loop of its own, which detects again)
- * finds the counters at zero.
+ * Held dynamics (ipm_kernels_box.hpp; the protocol is HeldDynamics below): the ROOT level runs every sweep of its loop with
+ * GqpOpts::hold bit 0 and lets its first affine forward sweep count the lanes with stage-invariant [B A]' (bit 1).  From the
+ * iteration after that one on, if EVERY tile of the batch is held, the factor launch and both rhs-only launches go to the entries
+ * that hold the block too (IpmKernels::fact_held, gqp::kh_factor; IpmKernels::rhs_held, gqp::kh_backrhs).  They read no flag: a
+ * mixed batch, the iteration that detects and every launch outside this loop (sub-levels, tail, sensitivities, ric_alg 0) keep
+ * K.fact and K.rhs, which fetch at every stage.  Sub-levels never set either bit and nothing of it is copied by compact_into.
  */
 /* side -> (stage, activity bit) of k_step_update, once per batch */
 static const int *side_map(ocp_qp_gpu_batch *b)
@@ -1761,19 +1799,60 @@ static const int *side_map(ocp_qp_gpu_batch *b)
 #define GQP_HOLD_SYNC 0
 #endif
 
-/* host wait for ONE event (the host simulation copies synchronously: nothing to wait for) */
-static inline void gqp_event_wait(hipEvent_t e)
+void HeldDynamics::begin(ocp_qp_gpu_batch *root, hipStream_t s, bool polish_loop)
 {
-#if defined(__HIPCC__)
-    HIPCHK(hipEventSynchronize(e));
-#else
-    (void) e;
+    b = root;
+    polish = polish_loop;
+    enabled = b->hold_dynamics && b->use_box && !b->wpi && !b->w16;
+    state = enabled ? DETECTING : COUNTED;
+    tiles = 0;
+    HIPCHK(hipMemsetAsync(b->D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+}
+
+void HeldDynamics::after_detect(hipStream_t s)
+{
+    if (state != DETECTING) return;
+    HIPCHK(hipMemcpyAsync(b->h_ints, b->D.tile_inv, sizeof(int) * (size_t) (b->Bp / 64), hipMemcpyDeviceToHost, s));
+    if (!ev) HIPCHK(hipEventCreate(&ev)); /* once per batch */
+    HIPCHK(hipEventRecord(ev, s));
+    state = AWAITING;
+#if GQP_HOLD_SYNC
+    HIPCHK(hipStreamSynchronize(s));
+    count();
 #endif
 }
 
-static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hipStream_t s, int it)
+void HeldDynamics::before_factor()
+{
+    if (state != AWAITING) return;
+    /* the counters were copied back behind the detecting sweep of the iteration before: wait for THAT copy, not for the stream
+     * -- the rhs and corrector launches of that iteration are still queued behind it, the device does not idle -- so that this
+     * factor launch can already be the held one */
+#if defined(__HIPCC__) /* (the host simulation copies synchronously: nothing to wait for) */
+    HIPCHK(hipEventSynchronize(ev));
+#endif
+    count();
+}
+
+void HeldDynamics::count()
+{
+    tiles = 0;
+    for (int q = 0; q < (b->B + 63) / 64; q++) tiles += b->h_ints[q] == std::min(64, b->B - 64 * q);
+    if (!polish) tiles_invariant = tiles;
+    state = COUNTED;
+}
+
+bool HeldDynamics::all_held() const { return enabled && state == COUNTED && tiles == (b->B + 63) / 64; }
+
+void HeldDynamics::end(hipStream_t s)
+{
+    if (b) HIPCHK(hipMemsetAsync(b->D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+}
+
+static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hipStream_t s, int it, bool polish)
 {
     const IpmKernels K = pick_kernels(b);
+    const bool top = b == root; /* per-class timing and held dynamics belong to the root level */
     GqpDev D = b->D;
     GqpOpts O = effective_opts(root->O, root);
     /* sixteen-lanes families, launch per sweep: the step is applied by a launch of its own (k_step_update) instead of a pass at
@@ -1785,16 +1864,10 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
      * GEN always, box classes up to 16,384 instances from N = 50 on.  ACADOS_AMD_EXT_UPDATE=0 / 1 forces the pass / the launch */
     const char *eext = getenv("ACADOS_AMD_EXT_UPDATE");
     const bool ext_update = b->w16 && (eext ? atoi(eext) != 0 : (b->w16_ng > 0 || (b->B <= 16384 && b->N >= 50)));
-    const bool hold = b == root && root->hold_dynamics && b->use_box && !b->wpi && !b->w16;
-    O.hold = hold ? 1 : 0;
-    bool detect = hold, counted = !hold; /* the first affine sweep detects; its counters are summed once they have arrived */
-    if (b == root)
-    {
-        root->n_tiles_invariant = 0;
-        root->n_rhs_held_launches = 0;
-        root->n_fact_held_launches = 0;
-        HIPCHK(hipMemsetAsync(D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
-    }
+    HeldDynamics none; /* a sub-level takes no part */
+    HeldDynamics &H = top ? root->held : none;
+    if (top) H.begin(root, s, polish);
+    O.hold = H.bits();
     GqpOpts Oc = O; /* options of the corrector-sweep launches */
     Oc.ext_update = ext_update ? 1 : 0;
     const int *smap = ext_update ? side_map(b) : nullptr;
@@ -1803,51 +1876,30 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
      * instances (row slot -> instance, GqpDev::perm) -- no data moves, the grid shrinks, every wave carries four live rows */
     const char *eperm = getenv("ACADOS_AMD_W16_PERM");
     const bool use_perm = b->w16 && !(eperm && atoi(eperm) == 0);
-    if (b == root && b->w16 && b->w16_solve && b->B <= root->solve_max && !D.perm)
+    if (top && b->w16 && b->w16_solve && b->B <= root->solve_max && !D.perm)
     {
         /* small batch: every 16-lane row runs this loop by itself inside one launch (kx_solve) */
-        prof.begin(1, s);
-        GQP_SWEEP_LAUNCH(b, b->w16_solve, 0, s, D, O, 0);
-        prof.end(s);
+        prof.timed(1, s, true, [&] { launch_sweep(b, Sweep{b->w16_solve, b->w16_shmem}, s, D, O, 0); });
         root->launches++;
         root->n_single_launch++;
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         if (*b->h_nact <= 0)
         {
-            if (b == root) HIPCHK(hipMemsetAsync(D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+            H.end(s);
             return;
         }
         /* (never taken: a row leaves the kernel only with its instance out of the RUNNING state) */
     }
-    const auto count_tiles = [&]() {
-        int full = 0;
-        for (int q = 0; q < (b->B + 63) / 64; q++) full += b->h_ints[q] == std::min(64, b->B - 64 * q);
-        root->n_tiles_invariant = full;
-        counted = true;
-    };
     for (;; it++)
     {
-        if (!detect && !counted)
-        {
-            /* the counters were copied back behind the detecting sweep of the iteration before: wait for THAT copy, not for the
-             * stream -- the rhs and corrector launches of that iteration are still queued behind it, the device does not idle --
-             * so that this factor launch can already be the held one */
-            gqp_event_wait(root->tiles_ev);
-            count_tiles();
-        }
+        H.before_factor();
         /* the held entries (factor here, the rhs pair below) read no flag: one tile that must fetch keeps K.fact / K.rhs for the
-         * whole launch, and so does every launch in front of the count */
-        const bool all_held = hold && counted && root->n_tiles_invariant == (b->B + 63) / 64;
-        const bool fact_held = all_held && K.fact_held;
-        if (b == root) prof.begin(1, s); /* per-class timing covers the root level only (full-batch launches) */
-        if (fact_held)
-        {
-            GQP_IPM_LAUNCH_SHM(b, K.fact_held, 0, s, D, O, 0);
-            root->n_fact_held_launches++;
-        }
-        else GQP_FACT_LAUNCH(b, K.fact, s, D, O, 0);
-        if (b == root) prof.end(s);
+         * whole launch, and so does every launch in front of the count (the iteration that detects) */
+        const bool all_held = H.all_held();
+        const bool fact_held = all_held && K.fact_held.fn, rhs_held = all_held && K.rhs_held.fn;
+        prof.timed(1, s, top, [&] { launch_sweep(b, fact_held ? K.fact_held : K.fact, s, D, O, 0); });
+        if (fact_held) H.fact_launches++;
         root->launches++;
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -1873,7 +1925,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
             /* the family's own finalize first: the general one-instance-per-lane kernels refresh the multipliers
              * of the fixed variables in every factor sweep and their finalize relies on that, the wave-per-instance
              * kernels compute them once at the end */
-            GQP_IPM_LAUNCH(tail, pick_kernels(tail).final_, s, tail->D);
+            launch_whole(tail, pick_kernels(tail).final_, s, tail->D);
             root->launches++;
             compact_back(b, s, SUB_TAIL, it);
             break;
@@ -1886,43 +1938,21 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
             compact_back(b, s, SUB_COMPACT, it);
             break;
         }
-        if (b == root) prof.begin(2, s);
-        {
-            GqpOpts Oa = O;
-            if (detect) Oa.hold |= 2;
-            GQP_SWEEP_LAUNCH(b, K.faff, b->shmem_fwd, s, D, Oa, 0);
-        }
-        if (b == root) prof.end(s);
-        if (detect)
-        {
-            HIPCHK(hipMemcpyAsync(b->h_ints, D.tile_inv, sizeof(int) * (size_t) (b->Bp / 64), hipMemcpyDeviceToHost, s));
-            if (!root->tiles_ev) HIPCHK(hipEventCreate(&root->tiles_ev)); /* once per batch */
-            HIPCHK(hipEventRecord(root->tiles_ev, s));
-            detect = false;
-#if GQP_HOLD_SYNC
-            HIPCHK(hipStreamSynchronize(s));
-            count_tiles();
-#endif
-        }
-        /* the rhs pair of this iteration: the held entry when EVERY tile of the root batch was found stage-invariant -- it reads no
-         * flag, so one tile that must fetch keeps K.rhs for the whole launch, and so does the iteration whose counters have not
-         * arrived yet (the one that detects) */
-        const bool rhs_held = all_held && K.rhs_held;
-        const kern_redo_t k_rhs = rhs_held ? K.rhs_held : K.rhs;
-        if (b == root) prof.begin(3, s);
-        GQP_SWEEP_LAUNCH(b, k_rhs, b->shmem, s, D, O, 0);
-        if (b == root) prof.end(s);
-        if (b == root) prof.begin(4, s);
-        GQP_SWEEP_LAUNCH(b, K.fcorr, b->shmem_fwd, s, D, Oc, 0);
-        if (b == root) prof.end(s);
+        GqpOpts Oa = O;
+        Oa.hold = H.bits(true);
+        prof.timed(2, s, top, [&] { launch_sweep(b, K.faff, s, D, Oa, 0); });
+        H.after_detect(s);
+        const Sweep &k_rhs = rhs_held ? K.rhs_held : K.rhs;
+        prof.timed(3, s, top, [&] { launch_sweep(b, k_rhs, s, D, O, 0); });
+        prof.timed(4, s, top, [&] { launch_sweep(b, K.fcorr, s, D, Oc, 0); });
         root->launches += 3;
         if (O.cond_pred_corr)
         {
-            GQP_SWEEP_LAUNCH(b, k_rhs, b->shmem, s, D, O, 1);
-            GQP_SWEEP_LAUNCH(b, K.fcorr, b->shmem_fwd, s, D, Oc, 1);
+            launch_sweep(b, k_rhs, s, D, O, 1);
+            launch_sweep(b, K.fcorr, s, D, Oc, 1);
             root->launches += 2;
         }
-        if (rhs_held) root->n_rhs_held_launches += O.cond_pred_corr ? 2 : 1;
+        if (rhs_held) H.rhs_launches += O.cond_pred_corr ? 2 : 1;
         if (ext_update)
         {
             /* (behind the redo pair: an instance whose corrector collapsed gets its step length there) */
@@ -1932,7 +1962,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         }
     }
     b->w16_slots = b->B; /* launches outside this loop (sensitivity passes) cover every instance again */
-    if (b == root) HIPCHK(hipMemsetAsync(D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+    H.end(s);
 }
 
 /*
@@ -1946,7 +1976,6 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
  * Cost: one iteration + one factor sweep over the instances selected -- in the one-instance-per-lane family over every 64-instance
  * tile that holds one.  Measured: profiles/NOTES.md round 6.
  */
-static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hipStream_t s, int it);
 static void polish_pass(ocp_qp_gpu_batch *b, Prof &prof, hipStream_t s)
 {
     b->n_polished = b->n_polish_reverted = 0;
@@ -1982,12 +2011,7 @@ static void polish_pass(ocp_qp_gpu_batch *b, Prof &prof, hipStream_t s)
     const GqpOpts Oeff = effective_opts(keep, b);
     b->O.tau_min = Oeff.tau_min; /* the barrier floor of the solve (derived from ITS tol_comp) */
     D.stat_inst = 0;             /* the statistics table keeps the solve's rows */
-    const int keep_inv = b->n_tiles_invariant; /* ("tiles_invariant" speaks of the solve) */
-    const int keep_held = b->n_rhs_held_launches, keep_fheld = b->n_fact_held_launches;
-    run_ipm(b, b, prof, s, 0);
-    b->n_tiles_invariant = keep_inv;
-    b->n_rhs_held_launches += keep_held; /* ("rhs_held_launches": every launch of the held entry, this pass's included) */
-    b->n_fact_held_launches += keep_fheld;
+    run_ipm(b, b, prof, s, 0, true); /* (a root loop of its own: it detects held dynamics again and adds to the held launch counts) */
     b->O = keep;
     D.stat_inst = keep_stat;
     hipLaunchKernelGGL(gqp::k_polish_restore, g64, blk, 0, s, D, Oeff, b->d_pol_status, b->d_pol_iter, b->d_pol_sc, b->d_pol_flag, b->d_pol_cnt + 1);
@@ -2223,7 +2247,7 @@ static int dense_solve(ocp_qp_gpu_batch *b)
     b->launches = (b->B + b->kd_slice - 1) / b->kd_slice;
     if (!b->kd_unsupported)
     {
-        GQP_IPM_LAUNCH(b, pick_kernels(b).final_, s, D);
+        launch_whole(b, pick_kernels(b).final_, s, D);
         b->launches++;
     }
     HIPCHK(hipEventRecord(b->ev1, s));
@@ -2316,6 +2340,7 @@ try
     b->n_compactions = 0;
     b->n_tail_switches = 0;
     b->n_single_launch = 0;
+    b->held.tiles_invariant = b->held.rhs_launches = b->held.fact_launches = 0;
     /* kernel classes: 0 init, 1 back_fact, 2 fwd_aff, 3 back_rhs, 4 fwd_corr, 5 finalize */
     b->prof_cls.clear();
     Prof prof;
@@ -2327,9 +2352,7 @@ try
     if (D.stat) HIPCHK(hipMemsetAsync(D.stat, 0, sizeof(double) * (size_t) b->stat_rows * GQP_STAT_COLS * b->stat_inst, s));
     if (O.warm_start < 2)
     {
-        prof.begin(0, s);
-        GQP_IPM_LAUNCH(b, ks->init, s, D, O);
-        prof.end(s);
+        prof.timed(0, s, true, [&] { launch_whole(b, ks->init, s, D, O); });
         b->launches++;
     }
     else
@@ -2345,7 +2368,7 @@ try
     if (b->polish) polish_pass(b, prof, s);
     b->factor_stale = b->n_tail_switches + b->n_compactions > 0;
     b->sens_open = false;
-    GQP_IPM_LAUNCH(b, pick_kernels(b).final_, s, D);
+    launch_whole(b, pick_kernels(b).final_, s, D);
     b->launches++;
     HIPCHK(hipEventRecord(b->ev1, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -2375,7 +2398,7 @@ static void refactor_at_solution(ocp_qp_gpu_batch *b)
     if (!b->d_saved_status) b->d_saved_status = dalloc<int>(b, b->Bp);
     GqpOpts O = effective_opts(b->O, b);
     hipLaunchKernelGGL(gqp::k_sens_prep, g64, blk, 0, s, b->D, O.tau_min, b->d_saved_status);
-    GQP_FACT_LAUNCH(b, pick_kernels(b).fact, s, b->D, O, 0);
+    launch_sweep(b, pick_kernels(b).fact, s, b->D, O, 0);
     hipLaunchKernelGGL(gqp::k_status_restore, g64, blk, 0, s, b->D, b->d_saved_status);
     HIPCHK(hipStreamSynchronize(s));
     b->factor_stale = false;
@@ -2467,8 +2490,8 @@ static void sens_pass(ocp_qp_gpu_batch *b, hipStream_t s)
     const IpmKernels K = pick_kernels(b);
     hipLaunchKernelGGL(gqp::k_sens_fixed, g64, blk, 0, s, b->D, b->sfix, 0);
     hipLaunchKernelGGL(gqp::k_sens_prep, g64, blk, 0, s, b->D, O.tau_min, b->d_saved_status);
-    GQP_SWEEP_LAUNCH(b, K.rhs, b->shmem, s, b->D, O, 2);
-    GQP_SWEEP_LAUNCH(b, K.fcorr, b->shmem_fwd, s, b->D, O, 2);
+    launch_sweep(b, K.rhs, s, b->D, O, 2);
+    launch_sweep(b, K.fcorr, s, b->D, O, 2);
     hipLaunchKernelGGL(gqp::k_sens_fixed, g64, blk, 0, s, b->D, b->sfix, 1);
     hipLaunchKernelGGL(gqp::k_status_restore, g64, blk, 0, s, b->D, b->d_saved_status);
 }
@@ -2701,9 +2724,9 @@ try
     if (!strcmp(f, "compactions")) return (double) b->n_compactions;
     if (!strcmp(f, "w16_tiles")) return (double) b->w16_tiles;
     if (!strcmp(f, "tail_switches")) return (double) b->n_tail_switches;
-    if (!strcmp(f, "tiles_invariant")) return (double) b->n_tiles_invariant;
-    if (!strcmp(f, "rhs_held_launches")) return (double) b->n_rhs_held_launches;
-    if (!strcmp(f, "fact_held_launches")) return (double) b->n_fact_held_launches;
+    if (!strcmp(f, "tiles_invariant")) return (double) b->held.tiles_invariant;
+    if (!strcmp(f, "rhs_held_launches")) return (double) b->held.rhs_launches;
+    if (!strcmp(f, "fact_held_launches")) return (double) b->held.fact_launches;
     if (!strcmp(f, "single_launch_solves")) return (double) b->n_single_launch;
     if (!strcmp(f, "cond_N_active")) return b->pcond_state == 1 ? (double) b->child->N : (double) b->N;
     if (!strcmp(f, "tol_comp_soft_scale")) return b->tol_comp_soft_scale;

@@ -15,41 +15,41 @@ typedef void (*kern_opts_t)(GqpDev, GqpOpts);
 typedef void (*kern_redo_t)(GqpDev, GqpOpts, int);
 typedef void (*kern_plain_t)(GqpDev);
 
+/* the four sweeps of the box-only fast path, index = XBOX (any box row on a state), and the entries for launches in which every
+ * 64-instance tile has stage-invariant [B A]' (held dynamics, ipm_kernels_box.hpp): gqp::kh_factor (A' and two rows of B' in LDS,
+ * the third in registers, W never stored; <8, 3> only) and gqp::kh_backrhs.  Held entries exist without XBOX only; null: none */
+struct BoxSweeps
+{
+    kern_redo_t fact[2], rhs[2], fwd_aff[2], fwd_corr[2], fact_held, rhs_held;
+};
+
 struct KernelSet
 {
     int NX, NU, NG, NS;
     kern_opts_t init;
     kern_redo_t back_fact, back_rhs, fwd_aff, fwd_corr;
     kern_plain_t finalize;
-    /* fast path for box-only QPs (ipm_kernels_box.hpp; ipm_kernels_box_small.hpp for nu + nx <= 6); index = XBOX (any box
-     * row on a state) */
-    kern_redo_t box_fact[2], box_rhs[2], box_fwd_aff[2], box_fwd_corr[2];
+    /* box-only QPs: the serving kernels (ipm_kernels_box_small.hpp where gqp::KbSmall holds, nu + nx <= 6: no held entries there;
+     * ipm_kernels_box.hpp otherwise; the run-time-shaped families put their own sweeps here) */
+    BoxSweeps box;
     kern_plain_t box_finalize;
     /* the ipm_kernels_box.hpp kernels for every shape (ACADOS_AMD_KB_SMALL=0: cross-check of the small-block kernels) */
-    kern_redo_t kb_fact[2], kb_rhs[2], kb_fwd_aff[2], kb_fwd_corr[2];
-    /* the rhs-only sweep with [B A]' held across the stages (gqp::kh_backrhs, no XBOX), for launches in which every tile is held:
-     * beside box_rhs[0] (null where the small-block kernels serve the shape) and beside kb_rhs[0]; null where not instantiated */
-    kern_redo_t box_rhs_held, kb_rhs_held;
-    /* the factor sweep of such launches (gqp::kh_factor: A' and two rows of B' in LDS, the third in registers, W never stored), in the
-     * same places; instantiated for <8, 3> only (kh_factor_for) */
-    kern_redo_t box_fact_held, kb_fact_held;
+    BoxSweeps kb;
 };
 
 #define GQP_KSET(NX, NU, NG, NS)                                                               \
     {NX, NU, NG, NS, gqp::k_init<NX, NU, NG, NS>, gqp::k_backward<NX, NU, NG, NS, true>,       \
      gqp::k_backward<NX, NU, NG, NS, false>, gqp::k_forward<NX, NU, NG, NS, false>,            \
      gqp::k_forward<NX, NU, NG, NS, true>, gqp::k_finalize<NX, NU, NG, NS>,                    \
-     {gqp::kb_factor_for<NX, NU, false>(), gqp::kb_factor_for<NX, NU, true>()},                \
-     {gqp::kb_backrhs_for<NX, NU, false>(), gqp::kb_backrhs_for<NX, NU, true>()},              \
-     {gqp::kb_forward_for<NX, NU, false, false>(), gqp::kb_forward_for<NX, NU, true, false>()}, \
-     {gqp::kb_forward_for<NX, NU, false, true>(), gqp::kb_forward_for<NX, NU, true, true>()},  \
+     {{gqp::kb_factor_for<NX, NU, false>(), gqp::kb_factor_for<NX, NU, true>()},               \
+      {gqp::kb_backrhs_for<NX, NU, false>(), gqp::kb_backrhs_for<NX, NU, true>()},             \
+      {gqp::kb_forward_for<NX, NU, false, false>(), gqp::kb_forward_for<NX, NU, true, false>()}, \
+      {gqp::kb_forward_for<NX, NU, false, true>(), gqp::kb_forward_for<NX, NU, true, true>()}, \
+      gqp::KbSmall<NX, NU>::value ? nullptr : gqp::kh_factor_for<NX, NU>(), gqp::KbSmall<NX, NU>::value ? nullptr : gqp::kh_backrhs_for<NX, NU>()}, \
      gqp::kb_finalize<NX, NU>,                                                                 \
-     {gqp::kb_factor<NX, NU, false>, gqp::kb_factor<NX, NU, true>},                            \
-     {gqp::kb_backrhs<NX, NU, false>, gqp::kb_backrhs<NX, NU, true>},                          \
-     {gqp::kb_forward<NX, NU, false, false>, gqp::kb_forward<NX, NU, true, false>},            \
-     {gqp::kb_forward<NX, NU, false, true>, gqp::kb_forward<NX, NU, true, true>},              \
-     gqp::KbSmall<NX, NU>::value ? nullptr : gqp::kh_backrhs_for<NX, NU>(), gqp::kh_backrhs_for<NX, NU>(),                           \
-     gqp::KbSmall<NX, NU>::value ? nullptr : gqp::kh_factor_for<NX, NU>(), gqp::kh_factor_for<NX, NU>()}
+     {{gqp::kb_factor<NX, NU, false>, gqp::kb_factor<NX, NU, true>}, {gqp::kb_backrhs<NX, NU, false>, gqp::kb_backrhs<NX, NU, true>}, \
+      {gqp::kb_forward<NX, NU, false, false>, gqp::kb_forward<NX, NU, true, false>},           \
+      {gqp::kb_forward<NX, NU, false, true>, gqp::kb_forward<NX, NU, true, true>}, gqp::kh_factor_for<NX, NU>(), gqp::kh_backrhs_for<NX, NU>()}}
 
 /* partial condensing: parent shape (NX, NU), blocks of at most BSMAX stages -> child shape
  * (NX, BSMAX*NU); kernels in pcond_kernels.hpp */

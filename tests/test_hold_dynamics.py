@@ -12,87 +12,32 @@ NaN, a hand-over).  They cannot see whether a consumer holds at all -- `tiles_in
 counters, and a kernel that fetched at every stage regardless would give the same outputs and the same scalar.  That the loads are gone
 is a measurement: HBM bytes per launch in profiles/r08_v1_pmc_traffic.json against profiles/r08_parent_pmc_traffic.json."""
 import os
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import hold_common
+from hold_common import B, LIB, MID, TIERS, assert_no_scratch, assert_same, built_kernel_facts, clib  # noqa: F401
 from oracle.oracle import OracleQp, default_opts
 
-TIERS = [pytest.param("hostsim", id="hostsim"), pytest.param("gpu", id="gpu", marks=pytest.mark.gpu)]
-N, NX, NU, B = 3, 8, 3, 130
-MID = 64 + 17            # an instance of the middle tile
+N = 3
 ZR, ZC = 3, 6            # entry of A that is +0.0 in every instance of the base batch
-FIELDS = ("x", "u", "pi", "lam", "t")
-
-
-@pytest.fixture
-def clib(request, monkeypatch):
-    monkeypatch.setenv("ACADOS_AMD_WPI", "0")   # one instance per lane whatever the batch size
-    return request.getfixturevalue("hostsim_lib" if request.param == "hostsim" else "gpu_lib")
-
-
-_BASE = {}
 
 
 def base_data():
-    """the batch with the same A, B at every stage (computed once, never changed: callers copy what they alter)"""
-    if not _BASE:
-        from acados_amd.generators import random_lqr_batch
-        d = random_lqr_batch(N=N, nx=NX, nu=NU, batch=B, seed=41)
-        d["A"][:, ZR, ZC] = 0.0
-        _BASE.update(d)
-    return _BASE
+    return hold_common.base_data(N, seed=41, zero_entry=(ZR, ZC))
 
 
 def make_batch(clib, a_stage=None, opts=None):
-    """a_stage: {stage: A of the whole batch at that stage} on top of the base batch"""
-    from acados_amd import OcpQpGpuBatch
-    from acados_amd.generators import fill_lqr_batch, lqr_dims
-    gb = OcpQpGpuBatch(lqr_dims(N, NX, NU), B, _clib=clib)
-    fill_lqr_batch(gb, base_data(), N)
-    for k, a in (a_stage or {}).items():
-        gb.set("A", k, a)
-    gb.opts_set("tol_stat", 1e-8)
-    for f, v in (opts or {}).items():
-        gb.opts_set(f, v)
-    return gb
+    return hold_common.make_batch(clib, base_data(), N, a_stage, opts)
 
 
 def outputs(gb):
-    out = {"iter": gb.info("iter").copy(), "status": gb.info("status").copy()}
-    for k in range(N + 1):
-        for f in FIELDS:
-            if (f == "pi" or f == "u") and k == N:
-                continue
-            out[f, k] = np.array(gb.get(f, k), copy=True)
-    return out
-
-
-_SOLVED = {}
+    return hold_common.outputs(gb, N)
 
 
 def solved(clib, hold, a_stage=None, opts=None, key=None):
-    """(batch, outputs) of one solve; runs named by `key` are computed once per library and shared between the tests"""
-    ck = (id(clib), hold, key)
-    if key is not None and ck in _SOLVED:
-        return _SOLVED[ck]
-    gb = make_batch(clib, a_stage, dict(opts or {}, hold_dynamics=hold))
-    gb.solve()
-    assert gb.kernel_name.startswith("1tpi-box<NX=8,NU=3"), gb.kernel_name
-    res = (gb, outputs(gb))
-    if key is not None:
-        _SOLVED[ck] = res
-    return res
-
-
-def assert_same(a, b, skip=()):
-    assert a.keys() == b.keys()
-    keep = np.array([i not in skip for i in range(B)])
-    for key in a:
-        assert np.array_equal(a[key][keep], b[key][keep], equal_nan=True), key
+    return hold_common.solved(clib, base_data(), N, hold, a_stage, opts, key)
 
 
 def altered(stage, r, c, value):
@@ -203,7 +148,6 @@ def test_compaction_with_held_dynamics(clib):
     assert_same(out_on, out_off)
 
 
-LIB = os.path.join(ROOT, "acados_amd", "csrc", "libacados_amd_qp.so")
 LIGHT = ("kb_forward<8, 3, false, false>", "kb_forward<8, 3, false, true>", "kb_backrhs<8, 3, false>")
 
 
@@ -212,25 +156,7 @@ def test_light_sweeps_hold_the_block_without_scratch():
     """the three light sweeps of C2 -- the two forward sweeps hold [B A]' (88 doubles more, live across the stage loop) -- stay in
     registers: no private segment, no spilled register -- read off the kernel descriptors of the built library (the same three kernels and fields as
     test_box_sweep_isa.py::test_c2_sweeps_stay_in_registers_and_fit_four_per_cu; kept here so that this file states the whole contract)"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import isa_lint
-    if not isa_lint.READELF:
-        pytest.skip("llvm-readelf not found")
-    found = {}
-    for co in isa_lint.code_objects(LIB):
-        with tempfile.NamedTemporaryFile(suffix=".co", delete=False) as f:
-            f.write(co)
-            tmp = f.name
-        try:
-            meta = isa_lint.metadata(tmp)
-        finally:
-            os.unlink(tmp)
-        names = isa_lint.demangle(list(meta))
-        for sym, md in meta.items():
-            for k in LIGHT:
-                if "gqp::" + k + "(" in names[sym]:
-                    found[k] = md
-    assert set(found) == set(LIGHT), sorted(found)
-    for k, md in found.items():
-        assert int(md.get("private_segment_fixed_size", 0)) == 0, (k, md)
-        assert int(md.get("vgpr_spill_count", 0)) == 0 and int(md.get("sgpr_spill_count", 0)) == 0, (k, md)
+    for k in LIGHT:
+        facts = built_kernel_facts(k, instructions=False)
+        assert facts is not None, k
+        assert_no_scratch(facts[0])

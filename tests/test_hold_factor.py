@@ -15,87 +15,26 @@ more for the exit test: max(iter) + 1 times.  The first of them runs in front of
 fact_held_launches = max(iter).  With a hand-over the root loop ends early, behind its m-th factor launch: m - 1 of them are held, and
 the rhs pairs of the iterations 2 .. m-1 are (two launches each, cond_pred_corr is on by default): fact_held = rhs_held / 2 + 1."""
 import os
-import re
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import hold_common
+from hold_common import B, LIB, MID, TIERS, TILES, assert_no_scratch, assert_same, built_kernel_facts, clib, outputs  # noqa: F401
 
-TIERS = [pytest.param("hostsim", id="hostsim"), pytest.param("gpu", id="gpu", marks=pytest.mark.gpu)]
-NX, NU, B = 8, 3, 130
-TILES = (B + 63) // 64
-MID = 64 + 17            # an instance of the middle tile
-FIELDS = ("x", "u", "pi", "lam", "t")
 ALONE = {"tail_max": 0}  # the root loop runs to the end by itself
 
 
-@pytest.fixture
-def clib(request, monkeypatch):
-    monkeypatch.setenv("ACADOS_AMD_WPI", "0")   # one instance per lane whatever the batch size
-    return request.getfixturevalue("hostsim_lib" if request.param == "hostsim" else "gpu_lib")
-
-
-_BASE = {}
-
-
 def base_data(N):
-    """the batch with the same A, B at every stage (computed once per horizon, never changed: callers copy what they alter)"""
-    if N not in _BASE:
-        from acados_amd.generators import random_lqr_batch
-        _BASE[N] = random_lqr_batch(N=N, nx=NX, nu=NU, batch=B, seed=43)
-    return _BASE[N]
+    return hold_common.base_data(N, seed=43)
 
 
 def make_batch(clib, N, a_stage=None, opts=None):
-    """a_stage: {stage: A of the whole batch at that stage} on top of the base batch"""
-    from acados_amd import OcpQpGpuBatch
-    from acados_amd.generators import fill_lqr_batch, lqr_dims
-    gb = OcpQpGpuBatch(lqr_dims(N, NX, NU), B, _clib=clib)
-    fill_lqr_batch(gb, base_data(N), N)
-    for k, a in (a_stage or {}).items():
-        gb.set("A", k, a)
-    gb.opts_set("tol_stat", 1e-8)
-    for f, v in (opts or {}).items():
-        gb.opts_set(f, v)
-    return gb
-
-
-def outputs(gb, N):
-    out = {"iter": gb.info("iter").copy(), "status": gb.info("status").copy()}
-    for k in range(N + 1):
-        for f in FIELDS:
-            if (f == "pi" or f == "u") and k == N:
-                continue
-            out[f, k] = np.array(gb.get(f, k), copy=True)
-    return out
-
-
-_SOLVED = {}
+    return hold_common.make_batch(clib, base_data(N), N, a_stage, opts)
 
 
 def solved(clib, N, hold, a_stage=None, opts=None, key=None):
-    """(batch, outputs) of one solve; runs named by `key` are computed once per library and shared between the tests"""
-    ck = (id(clib), N, hold, key)
-    if key is not None and ck in _SOLVED:
-        return _SOLVED[ck]
-    gb = make_batch(clib, N, a_stage, dict(opts or {}, hold_dynamics=hold))
-    gb.solve()
-    assert gb.kernel_name.startswith("1tpi-box<NX=8,NU=3"), gb.kernel_name
-    res = (gb, outputs(gb, N))
-    if key is not None:
-        _SOLVED[ck] = res
-    return res
-
-
-def assert_same(a, b, skip=()):
-    assert a.keys() == b.keys()
-    keep = np.array([i not in skip for i in range(B)])
-    for key in a:
-        assert np.array_equal(a[key][keep], b[key][keep], equal_nan=True), key
+    return hold_common.solved(clib, base_data(N), N, hold, a_stage, opts, key)
 
 
 def fheld(gb):
@@ -219,7 +158,6 @@ def test_statistics_rows_of_a_held_solve(clib):
         assert np.array_equal(s_on[:, cols], s_off[:, cols], equal_nan=True), inst
 
 
-LIB = os.path.join(ROOT, "acados_amd", "csrc", "libacados_amd_qp.so")
 HELD = "kh_factor<8, 3>"
 
 
@@ -227,38 +165,30 @@ HELD = "kh_factor<8, 3>"
 def test_held_entry_is_built_without_scratch():
     """the held entry of C2's shape is in the built library: no private segment, no spilled register, static LDS that lets four
     single-wave blocks share a CU's 160 KB, no scratch instruction in its code (read the way tests/test_box_sweep_isa.py does)"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import isa_lint
-    if not isa_lint.READELF or not isa_lint.OBJDUMP:
-        pytest.skip("llvm-readelf / llvm-objdump not found")
-    found = {}
-    for co in isa_lint.code_objects(LIB):
-        with tempfile.NamedTemporaryFile(suffix=".co", delete=False) as f:
-            f.write(co)
-            tmp = f.name
-        try:
-            meta = isa_lint.metadata(tmp)
-            notes = subprocess.run([isa_lint.READELF, "--notes", tmp], capture_output=True, text=True).stdout
-            dis = isa_lint.kernels(subprocess.run([isa_lint.OBJDUMP, "-d", tmp], capture_output=True, text=True).stdout)
-        finally:
-            os.unlink(tmp)
-        # static LDS per kernel: .group_segment_fixed_size precedes .name / .symbol inside a kernel's metadata entry
-        lds, cur = {}, None
-        for ln in notes.splitlines():
-            m = re.match(r"\s*-?\s*\.(group_segment_fixed_size|symbol):\s*(\S+)", ln)
-            if m and m.group(1) == "group_segment_fixed_size":
-                cur = int(m.group(2))
-            elif m and cur is not None:
-                lds[m.group(2).strip("'\"").replace(".kd", "")] = cur
-                cur = None
-        names = isa_lint.demangle(list(meta))
-        for sym, md in meta.items():
-            if "gqp::" + HELD + "(" in names[sym]:
-                found[HELD] = (md, lds.get(sym), dis.get(sym, []))
-    assert set(found) == {HELD}, sorted(found)
-    md, lds_bytes, ins = found[HELD]
+    facts = built_kernel_facts(HELD)
+    assert facts is not None, HELD
+    md, lds_bytes, ins = facts
+    if ins is None:
+        pytest.skip("llvm-objdump not found")
     assert ins, HELD
-    assert int(md.get("private_segment_fixed_size", 0)) == 0, md
-    assert int(md.get("vgpr_spill_count", 0)) == 0 and int(md.get("sgpr_spill_count", 0)) == 0, md
+    assert_no_scratch(md)
     assert lds_bytes is not None and lds_bytes <= 40960, lds_bytes
     assert not any("scratch_" in t for t in ins)
+
+
+@pytest.mark.parametrize("clib", TIERS, indirect=True)
+def test_polish_pass_keeps_the_counts_of_the_solve(clib):
+    """the polish pass is a root loop of its own (iteration counter 0 against iter_max 1): its first factor launch runs in front of its
+    detecting sweep, its second and last one is held, and the rhs pair between them is the detecting iteration's and fetches.  So a
+    polished solve reports the plain solve's `tiles_invariant` (the scalar speaks of the solve, the pass does not overwrite it), its
+    `fact_held_launches` plus one and its `rhs_held_launches`.  polish_ratio 0 selects every instance: on the device a wave without a
+    running lane leaves the detecting sweep before it counts (GQP_WAVE_ANY; the host simulation treats every wave as live), and the
+    pass holds only if all three tiles count"""
+    N = 3
+    plain = solved(clib, N, 1, opts=ALONE, key="alone")[0]
+    pol = solved(clib, N, 1, opts=dict(ALONE, polish=1, polish_ratio=0.0))[0]
+    print("polished", pol.scalar("polished"), "tiles", pol.scalar("tiles_invariant"), "fact held", fheld(plain), fheld(pol), "rhs held", rheld(plain), rheld(pol))
+    assert int(pol.scalar("polished")) == B                 # (every tile has running lanes in the loop of the pass)
+    assert int(pol.scalar("tiles_invariant")) == TILES == 3
+    assert fheld(pol) == fheld(plain) + 1
+    assert rheld(pol) == rheld(plain) > 0

@@ -10,84 +10,24 @@ sources under g++, one lane at a time) and `gpu` (the product library).  Horizon
 that reuses the block, stage 0), N = 2 (exactly one stage reuses) and N = 1 (none does): the shapes at which a wrong "fetch at"
 condition shows."""
 import os
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
-TIERS = [pytest.param("hostsim", id="hostsim"), pytest.param("gpu", id="gpu", marks=pytest.mark.gpu)]
-NX, NU, B = 8, 3, 130
-TILES = (B + 63) // 64
-MID = 64 + 17            # an instance of the middle tile
-FIELDS = ("x", "u", "pi", "lam", "t")
-
-
-@pytest.fixture
-def clib(request, monkeypatch):
-    monkeypatch.setenv("ACADOS_AMD_WPI", "0")   # one instance per lane whatever the batch size
-    return request.getfixturevalue("hostsim_lib" if request.param == "hostsim" else "gpu_lib")
-
-
-_BASE = {}
+import hold_common
+from hold_common import LIB, MID, TIERS, TILES, assert_no_scratch, assert_same, built_kernel_facts, clib, outputs  # noqa: F401
 
 
 def base_data(N):
-    """the batch with the same A, B at every stage (computed once per horizon, never changed: callers copy what they alter)"""
-    if N not in _BASE:
-        from acados_amd.generators import random_lqr_batch
-        _BASE[N] = random_lqr_batch(N=N, nx=NX, nu=NU, batch=B, seed=41)
-    return _BASE[N]
+    return hold_common.base_data(N, seed=41)
 
 
 def make_batch(clib, N, a_stage=None, opts=None):
-    """a_stage: {stage: A of the whole batch at that stage} on top of the base batch"""
-    from acados_amd import OcpQpGpuBatch
-    from acados_amd.generators import fill_lqr_batch, lqr_dims
-    gb = OcpQpGpuBatch(lqr_dims(N, NX, NU), B, _clib=clib)
-    fill_lqr_batch(gb, base_data(N), N)
-    for k, a in (a_stage or {}).items():
-        gb.set("A", k, a)
-    gb.opts_set("tol_stat", 1e-8)
-    for f, v in (opts or {}).items():
-        gb.opts_set(f, v)
-    return gb
-
-
-def outputs(gb, N):
-    out = {"iter": gb.info("iter").copy(), "status": gb.info("status").copy()}
-    for k in range(N + 1):
-        for f in FIELDS:
-            if (f == "pi" or f == "u") and k == N:
-                continue
-            out[f, k] = np.array(gb.get(f, k), copy=True)
-    return out
-
-
-_SOLVED = {}
+    return hold_common.make_batch(clib, base_data(N), N, a_stage, opts)
 
 
 def solved(clib, N, hold, a_stage=None, opts=None, key=None):
-    """(batch, outputs) of one solve; runs named by `key` are computed once per library and shared between the tests"""
-    ck = (id(clib), N, hold, key)
-    if key is not None and ck in _SOLVED:
-        return _SOLVED[ck]
-    gb = make_batch(clib, N, a_stage, dict(opts or {}, hold_dynamics=hold))
-    gb.solve()
-    assert gb.kernel_name.startswith("1tpi-box<NX=8,NU=3"), gb.kernel_name
-    res = (gb, outputs(gb, N))
-    if key is not None:
-        _SOLVED[ck] = res
-    return res
-
-
-def assert_same(a, b, skip=()):
-    assert a.keys() == b.keys()
-    keep = np.array([i not in skip for i in range(B)])
-    for key in a:
-        assert np.array_equal(a[key][keep], b[key][keep], equal_nan=True), key
+    return hold_common.solved(clib, base_data(N), N, hold, a_stage, opts, key)
 
 
 def held(gb):
@@ -181,7 +121,6 @@ def test_nan_stays_with_its_instance(clib, where):
             assert held(gb) == 0
 
 
-LIB = os.path.join(ROOT, "acados_amd", "csrc", "libacados_amd_qp.so")
 HELD = "kh_backrhs<8, 3>"
 
 
@@ -189,24 +128,6 @@ HELD = "kh_backrhs<8, 3>"
 def test_held_entry_is_built_without_scratch():
     """the held entry of C2's shape is in the built library and stays in registers: no private segment, no spilled register -- read
     off its kernel descriptor"""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import isa_lint
-    if not isa_lint.READELF:
-        pytest.skip("llvm-readelf not found")
-    found = {}
-    for co in isa_lint.code_objects(LIB):
-        with tempfile.NamedTemporaryFile(suffix=".co", delete=False) as f:
-            f.write(co)
-            tmp = f.name
-        try:
-            meta = isa_lint.metadata(tmp)
-        finally:
-            os.unlink(tmp)
-        names = isa_lint.demangle(list(meta))
-        for sym, md in meta.items():
-            if "gqp::" + HELD + "(" in names[sym]:
-                found[HELD] = md
-    assert set(found) == {HELD}, sorted(found)
-    md = found[HELD]
-    assert int(md.get("private_segment_fixed_size", 0)) == 0, md
-    assert int(md.get("vgpr_spill_count", 0)) == 0 and int(md.get("sgpr_spill_count", 0)) == 0, md
+    facts = built_kernel_facts(HELD, instructions=False)
+    assert facts is not None, HELD
+    assert_no_scratch(facts[0])

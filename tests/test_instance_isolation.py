@@ -339,6 +339,31 @@ def test_failed_instances_with_tail_hand_over(clib, monkeypatch):
 
 
 @pytest.mark.parametrize("clib", TIERS, indirect=True)
+def test_tail_hand_over_from_the_general_rows_family(clib, monkeypatch):
+    """1tpi-gen, clean data, six instances in one block of the root; tail_max 5, tail_div 1: as soon as one has converged the others
+    go to the tail, at least two of them.  The general one-instance-per-lane finalize takes the multipliers of the fixed variables
+    from the last factor sweep; for the instances that finished on the tail that sweep ran there, and the tail's own finalize -- one
+    workgroup per instance with the tail's LDS, not the root's 64 instances per block -- computes them before the copy back.  Every
+    instance passes the independent residual kernel and agrees with the oracle at 1e-8, multipliers included"""
+    row = "1tpi-gen"
+    gb = _make(clib, monkeypatch, row, tail_max=5)
+    gb.opts_set("tail_div", 1)
+    assert gb.solve() == 0
+    _check_family(gb, row)
+    assert int(gb.scalar("tail_switches")) == 1
+    snap = _snapshot(gb)
+    print("iterations", snap["iter"])
+    assert np.all(snap["status"] == 0) and np.sum(snap["iter"] > snap["iter"].min()) >= 2      # two or more went to the tail
+    nrm = snap["res_nrm"]
+    assert np.all(np.isfinite(nrm)) and nrm.max() <= KKT_TOL, nrm
+    qps = _qps(ROWS[row]["qps"])
+    for i in range(len(qps)):
+        o = _oracle(ROWS[row]["qps"], i)
+        assert o.status == 0
+        compare_with_oracle(lambda k, f: snap[(f, k)][i], o, qps[i], 1e-8)
+
+
+@pytest.mark.parametrize("clib", TIERS, indirect=True)
 @pytest.mark.parametrize("row", list(ROWS))
 def test_truncated_iterate_matches_oracle(clib, monkeypatch, row):
     """iter_max = 3 on clean data: every instance reports ACADOS_MAXITER (2) with iter == 3, and the iterate that comes back (x, u,
@@ -461,3 +486,38 @@ def test_nan_in_an_entry_the_solve_never_reads(clib, request, monkeypatch, row):
     for k in range(qp.N + 1):
         for f in ("x", "u"):
             assert np.array_equal(snap[(f, k)][1], twin[(f, k)][1])   # the entry is not read at all
+
+
+@pytest.mark.parametrize("clib", TIERS, indirect=True)
+def test_dense_list_with_a_partly_filled_last_workgroup(clib, monkeypatch):
+    """w16-box at N = 2, batch 7 (the second workgroup carries three rows), launch per sweep.  Instances 1, 3 and 6 start close to the
+    origin (x0 scaled by 1e-3: no input bound comes near) and converge first, so at least two have converged while another still
+    iterates: the dense list of the live instances (ACADOS_AMD_W16_PERM, run_ipm) comes on and the grid of the sweeps shrinks.  Every
+    output is bit for bit that of the solve without the list"""
+    from acados_amd import OcpQpGpuBatch
+    from acados_amd.generators import fill_lqr_batch, lqr_dims, random_lqr_batch
+    N, B = 2, 7
+    data = random_lqr_batch(N=N, nx=8, nu=3, batch=B, seed=38)
+    data["x0"][[1, 3, 6]] *= 1e-3
+    for k, v in W16.items():
+        monkeypatch.setenv(k, v)
+    out = {}
+    for perm in ("1", "0"):
+        monkeypatch.setenv("ACADOS_AMD_W16_PERM", perm)
+        gb = OcpQpGpuBatch(lqr_dims(N, 8, 3), B, _clib=clib)
+        fill_lqr_batch(gb, data, N)
+        gb.opts_set("tol_stat", 1e-8)
+        gb.opts_set("solve_max", 0)
+        assert gb.solve() == 0
+        assert gb.kernel_name.startswith("w16-box<NX=8,NU=3>") and int(gb.scalar("single_launch_solves")) == 0, gb.kernel_name
+        out[perm] = {"iter": gb.info("iter").copy(), "status": gb.info("status").copy()}
+        for k in range(N + 1):
+            for f in ("x", "u", "pi", "lam", "t"):
+                if not (f in ("u", "pi") and k == N):
+                    out[perm][f, k] = np.array(gb.get(f, k), copy=True)
+    it = np.sort(out["1"]["iter"])
+    print("iterations", out["1"]["iter"])
+    assert it[1] < it[-1]          # two have converged while one still iterates: 6 * nact <= 5 * 7, the list is on
+    assert out["1"].keys() == out["0"].keys()
+    for key in out["1"]:
+        assert np.array_equal(out["1"][key], out["0"][key]), key
