@@ -160,13 +160,34 @@ struct BulkMap
  * after_detect() copies the counters back and records an event behind the copy; before_factor(), at the top of the next iteration,
  * waits for that event -- not for the stream -- and counts the full tiles; from then on all_held() says whether a launch may take
  * the held entries; end() zeroes tile_inv again, so every other launch of these kernels (sub-levels, sensitivities, a later solve)
- * finds the counters at zero.  Methods: in front of run_ipm. */
+ * finds the counters at zero.
+ *   Verdicts outlive the solve.  What the detector finds is a property of the resident matrices: every writer of GqpDev::BAt /
+ *   RSQ of a root batch bumps ver_dyn / ver_hess (data_written), a solve's count is stored with the version it was taken at, and a
+ *   root loop that finds the stored version current starts COUNTED -- counters copied from d_kept, no detect bit, no read-back, no
+ *   event wait, iteration 1 on the held entries.  The polish pass always detects for itself.  A count is stored only where every
+ *   instance was still running when the detecting sweep was launched (a wave without a running lane leaves that sweep before it
+ *   counts: such a count says less than the data) or where it is full anyway.
+ *   Held Hessian: where every tile is held and the held factor entry exists, hessian_verdict() runs gqp::k_hess_invariant once per
+ *   ver_hess and the held factor launches read one copy of RSQ (GqpOpts::hold bit 2) while the verdict is current and positive.
+ * Methods: in front of run_ipm. */
 struct HeldDynamics
 {
-    /* the last solve: scalars "tiles_invariant" (of the solve's own loop), "fact_held_launches" / "rhs_held_launches" (launches of
-     * IpmKernels::fact_held / rhs_held, the polish pass's included); reset by ocp_qp_gpu_batch_solve */
-    int tiles_invariant = 0, fact_launches = 0, rhs_launches = 0;
+    /* the last solve: scalars "tiles_invariant" (of the solve's own loop, or the stored count it started from), "fact_held_launches"
+     * / "rhs_held_launches" (launches of IpmKernels::fact_held / rhs_held, the polish pass's included), "hess_held_launches" (those
+     * of fact_held with hold bit 2), "hess_detector_runs", "detecting_sweeps" (1 where the solve's own loop ran the detecting sweep,
+     * 0 where it started from a stored count); reset by ocp_qp_gpu_batch_solve */
+    int tiles_invariant = 0, fact_launches = 0, rhs_launches = 0, hess_launches = 0, hess_detects = 0, detects = 0;
     hipEvent_t ev = nullptr; /* recorded behind the read-back of the counters */
+    /* the data and what is known about it (0 is no version: nothing is known at the start) */
+    unsigned ver_dyn = 1, ver_hess = 1;  /* versions of the arrays behind [B A]' and of RSQ */
+    unsigned kept_at = 0;                /* ver_dyn the stored count was taken at */
+    int kept_tiles = 0;                  /* ... the count, its counters in d_kept */
+    int *d_kept = nullptr;               /* [Bp / 64], beside GqpDev::tile_inv */
+    unsigned hess_at = 0;                /* ver_hess the Hessian verdict was taken at */
+    bool hess_inv = false;               /* ... the verdict: RSQ of every instance is the same at the stages 0 .. N-1 */
+    int *d_hess_cnt = nullptr;           /* [Bp / 64] agreeing lanes per tile, written by k_hess_invariant */
+    unsigned pending_ver = 0;            /* ver_dyn at the detecting sweep of this loop; 0: its count is not to be stored */
+    bool complete = false;               /* ... every instance was running when that sweep was launched: every wave counted */
     /* the root loop that runs */
     ocp_qp_gpu_batch *b = nullptr; /* null: a sub-level's record, which does nothing */
     bool enabled = false;          /* option hold_dynamics on a one-instance-per-lane box batch */
@@ -177,11 +198,17 @@ struct HeldDynamics
     void begin(ocp_qp_gpu_batch *root, hipStream_t s, bool polish_loop);
     /* GqpOpts::hold of a launch of this loop: bit 0 tiles with a full counter hold; bit 1 (the affine sweep while DETECTING) count */
     int bits(bool affine_sweep = false) const { return !enabled ? 0 : (affine_sweep && state == DETECTING) ? 3 : 1; }
-    void after_detect(hipStream_t s);
-    void before_factor();
+    void after_detect(hipStream_t s, bool all_running);
+    void before_factor(bool fact_entry);
+    void stream_drained();
     void count();
     bool all_held() const;
+    /* is the Hessian of every instance stage-invariant?  Asked where a held factor launch is about to go out; runs the detector
+     * (one launch, one read-back, one wait for the stream) where ver_hess has moved since the stored verdict */
+    bool hessian_verdict(hipStream_t s);
     void end(hipStream_t s);
+    /* a writer of a root batch's matrices: the arrays behind [B A]' (dyn) and / or RSQ (hess) are not what they were */
+    void data_written(bool dyn, bool hess) { if (dyn) ver_dyn++; if (hess) ver_hess++; if (!ver_dyn) ver_dyn = 1; if (!ver_hess) ver_hess = 1; }
 };
 
 struct ocp_qp_gpu_batch
@@ -294,7 +321,8 @@ struct ocp_qp_gpu_batch
     int n_tail_switches = 0;
     /* held dynamics of the one-instance-per-lane box sweeps (ipm_kernels_box.hpp; run_ipm) */
     int hold_dynamics = 1;               /* option: 1 = tiles whose [B A]' is found stage-invariant keep it in registers, 0 = never */
-    HeldDynamics held;                   /* the protocol of the root loop and what the last solve counted */
+    int hold_hessian = 1;                /* option: 1 = held factor launches read one copy of a stage-invariant RSQ, 0 = every stage its own */
+    HeldDynamics held;                   /* the protocol of the root loop, what the last solve counted and what is known of the data */
     /* solution sensitivities / factor at the solution */
     bool factor_stale = false;           /* the last solve finished instances on a sub-level: Lf of the root is not theirs */
     bool sens_open = false;              /* seeds are being collected (rg, rb, rd hold seeds, not residuals) */
@@ -624,6 +652,8 @@ void finalize_structure(ocp_qp_gpu_batch *b)
     D.iter = dalloc<int>(b, Bp); D.status = dalloc<int>(b, Bp);
     D.n_active = dalloc<int>(b, 1);
     D.tile_inv = dalloc<int>(b, (size_t) Bp / 64);
+    b->held.d_kept = dalloc<int>(b, (size_t) Bp / 64);
+    b->held.d_hess_cnt = dalloc<int>(b, (size_t) Bp / 64);
     b->stat_inst = b->B < 64 ? b->B : 64;
     b->stat_rows = 0;
     D.stat = nullptr; D.stat_inst = 0; D.stat_rows = 0;
@@ -1245,6 +1275,7 @@ try
         if (len == 0) continue;
         if (src_len != len) { src = stage_in(b, data, (size_t) b->B * len, is_device); src_len = len; }
         int *dm = upload_map(b, map);
+        b->held.data_written(arr.p == b->D.BAt.p, arr.p == b->D.RSQ.p); /* fields A, B / Q, R, S: stored verdicts are of older data */
         hipLaunchKernelGGL(gqp::k_scatter, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, arr);
         if (arr2.p)
         {
@@ -1337,6 +1368,7 @@ try
     else if (!strcmp(f, "compact_min")) b->compact_min = *i;
     else if (!strcmp(f, "tail_max")) b->tail_max = *i;
     else if (!strcmp(f, "hold_dynamics")) b->hold_dynamics = *i != 0;
+    else if (!strcmp(f, "hold_hessian")) b->hold_hessian = *i != 0;
     else if (!strcmp(f, "tail_div")) b->tail_div = *i < 1 ? 1 : *i;
     else if (!strcmp(f, "solve_max")) b->solve_max = *i;
     else if (!strcmp(f, "cond_N"))
@@ -1591,6 +1623,7 @@ static void pcond_setup(ocp_qp_gpu_batch *b)
 static void pcond_launch(ocp_qp_gpu_batch *b, bool expand)
 {
     ocp_qp_gpu_batch *c = b->child;
+    if (!expand) c->held.data_written(true, true); /* the condensing kernels write the child's matrices: it is the root of its own solve */
     if (!expand && b->pcz && b->pc_rt && b->AW <= 1 && c->AW <= 1)
     {
         const dim3 grid((b->B + 3) / 4, b->pmap.N2 + 1);
@@ -1804,15 +1837,33 @@ void HeldDynamics::begin(ocp_qp_gpu_batch *root, hipStream_t s, bool polish_loop
     b = root;
     polish = polish_loop;
     enabled = b->hold_dynamics && b->use_box && !b->wpi && !b->w16;
+    pending_ver = 0;
+    const size_t bytes = sizeof(int) * (size_t) (b->Bp / 64);
+    if (enabled && !polish && kept_at == ver_dyn)
+    {
+        /* the matrices are the ones the stored count was taken on: the loop starts where the detecting iteration would leave it */
+        state = COUNTED;
+        tiles = tiles_invariant = kept_tiles;
+        HIPCHK(hipMemcpyAsync(b->D.tile_inv, d_kept, bytes, hipMemcpyDeviceToDevice, s));
+        return;
+    }
     state = enabled ? DETECTING : COUNTED;
     tiles = 0;
-    HIPCHK(hipMemsetAsync(b->D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+    HIPCHK(hipMemsetAsync(b->D.tile_inv, 0, bytes, s));
 }
 
-void HeldDynamics::after_detect(hipStream_t s)
+void HeldDynamics::after_detect(hipStream_t s, bool all_running)
 {
     if (state != DETECTING) return;
     HIPCHK(hipMemcpyAsync(b->h_ints, b->D.tile_inv, sizeof(int) * (size_t) (b->Bp / 64), hipMemcpyDeviceToHost, s));
+    if (!polish)
+    {
+        /* the counters as they stand, for the solves to come (count() decides whether they are kept) */
+        HIPCHK(hipMemcpyAsync(d_kept, b->D.tile_inv, sizeof(int) * (size_t) (b->Bp / 64), hipMemcpyDeviceToDevice, s));
+        pending_ver = ver_dyn;
+        complete = all_running;
+        detects++;
+    }
     if (!ev) HIPCHK(hipEventCreate(&ev)); /* once per batch */
     HIPCHK(hipEventRecord(ev, s));
     state = AWAITING;
@@ -1822,9 +1873,12 @@ void HeldDynamics::after_detect(hipStream_t s)
 #endif
 }
 
-void HeldDynamics::before_factor()
+void HeldDynamics::before_factor(bool fact_entry)
 {
     if (state != AWAITING) return;
+    /* a shape without a held factor entry has nothing to choose here: its count is taken behind the wait for the stream that
+     * follows the factor launch anyway (stream_drained), in time for the rhs pair */
+    if (!fact_entry) return;
     /* the counters were copied back behind the detecting sweep of the iteration before: wait for THAT copy, not for the stream
      * -- the rhs and corrector launches of that iteration are still queued behind it, the device does not idle -- so that this
      * factor launch can already be the held one */
@@ -1840,9 +1894,38 @@ void HeldDynamics::count()
     for (int q = 0; q < (b->B + 63) / 64; q++) tiles += b->h_ints[q] == std::min(64, b->B - 64 * q);
     if (!polish) tiles_invariant = tiles;
     state = COUNTED;
+    /* kept for the solves to come: a full count always; a partial one only where no wave can have left the sweep uncounted */
+    if (pending_ver && (complete || tiles == (b->B + 63) / 64))
+    {
+        kept_at = pending_ver;
+        kept_tiles = tiles;
+    }
+    pending_ver = 0;
+}
+
+void HeldDynamics::stream_drained()
+{
+    if (state == AWAITING) count();
 }
 
 bool HeldDynamics::all_held() const { return enabled && state == COUNTED && tiles == (b->B + 63) / 64; }
+
+bool HeldDynamics::hessian_verdict(hipStream_t s)
+{
+    if (hess_at == ver_hess) return hess_inv;
+    const int nt = (b->B + 63) / 64;
+    int *h = b->h_ints; /* (the counters of the dynamics have been summed: count() is behind us) */
+    HIPCHK(hipMemsetAsync(d_hess_cnt, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+    hipLaunchKernelGGL(gqp::k_hess_invariant, dim3(nt), dim3(64), 0, s, b->D, d_hess_cnt);
+    HIPCHK(hipMemcpyAsync(h, d_hess_cnt, sizeof(int) * (size_t) nt, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    int full = 0;
+    for (int q = 0; q < nt; q++) full += h[q] == std::min(64, b->B - 64 * q);
+    hess_inv = full == nt;
+    hess_at = ver_hess;
+    hess_detects++;
+    return hess_inv;
+}
 
 void HeldDynamics::end(hipStream_t s)
 {
@@ -1893,16 +1976,22 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
     }
     for (;; it++)
     {
-        H.before_factor();
+        H.before_factor(K.fact_held.fn != nullptr);
         /* the held entries (factor here, the rhs pair below) read no flag: one tile that must fetch keeps K.fact / K.rhs for the
          * whole launch, and so does every launch in front of the count (the iteration that detects) */
         const bool all_held = H.all_held();
         const bool fact_held = all_held && K.fact_held.fn, rhs_held = all_held && K.rhs_held.fn;
-        prof.timed(1, s, top, [&] { launch_sweep(b, fact_held ? K.fact_held : K.fact, s, D, O, 0); });
+        /* ... and where the packed Hessian is stage-invariant too, the held factor launch reads one copy of it (hold bit 2) */
+        const bool hess_held = fact_held && root->hold_hessian && H.hessian_verdict(s);
+        GqpOpts Of = O;
+        if (hess_held) Of.hold |= 4;
+        prof.timed(1, s, top, [&] { launch_sweep(b, fact_held ? K.fact_held : K.fact, s, D, Of, 0); });
         if (fact_held) H.fact_launches++;
+        if (hess_held) H.hess_launches++;
         root->launches++;
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
+        H.stream_drained();
         const int nact = *b->h_nact;
         if (root->print_level > 1) printf("acados_amd: ipm iter %d level size %d active %d\n", it, b->B, nact);
         if (nact <= 0 || it > O.iter_max) break;
@@ -1941,7 +2030,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         GqpOpts Oa = O;
         Oa.hold = H.bits(true);
         prof.timed(2, s, top, [&] { launch_sweep(b, K.faff, s, D, Oa, 0); });
-        H.after_detect(s);
+        H.after_detect(s, nact == b->B);
         const Sweep &k_rhs = rhs_held ? K.rhs_held : K.rhs;
         prof.timed(3, s, top, [&] { launch_sweep(b, k_rhs, s, D, O, 0); });
         prof.timed(4, s, top, [&] { launch_sweep(b, K.fcorr, s, D, Oc, 0); });
@@ -2120,6 +2209,7 @@ static void sub_batch_load(ocp_qp_gpu_batch *b, const SubBatch &sb, int cnt, hip
     ocp_qp_gpu_batch *c = sb.c;
     c->B = cnt; /* the sub-batch works on `cnt` slots of its capacity */
     c->D.B = cnt;
+    c->held.data_written(true, true); /* (no sub-batch holds today -- a wave-per-instance family, or a level below the root; kept right all the same) */
     sub_copy(b, sb, g_state_arrays, cnt, 0, s);
     copy_level(b->D.amask, c->D.amask, sb.d_list, cnt, 0, s);
     hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), dim3(64), 0, s, b->D, c->D, sb.d_list, cnt, 0);
@@ -2340,7 +2430,7 @@ try
     b->n_compactions = 0;
     b->n_tail_switches = 0;
     b->n_single_launch = 0;
-    b->held.tiles_invariant = b->held.rhs_launches = b->held.fact_launches = 0;
+    b->held.tiles_invariant = b->held.rhs_launches = b->held.fact_launches = b->held.hess_launches = b->held.hess_detects = b->held.detects = 0;
     /* kernel classes: 0 init, 1 back_fact, 2 fwd_aff, 3 back_rhs, 4 fwd_corr, 5 finalize */
     b->prof_cls.clear();
     Prof prof;
@@ -2727,6 +2817,9 @@ try
     if (!strcmp(f, "tiles_invariant")) return (double) b->held.tiles_invariant;
     if (!strcmp(f, "rhs_held_launches")) return (double) b->held.rhs_launches;
     if (!strcmp(f, "fact_held_launches")) return (double) b->held.fact_launches;
+    if (!strcmp(f, "hess_held_launches")) return (double) b->held.hess_launches;
+    if (!strcmp(f, "hess_detector_runs")) return (double) b->held.hess_detects;
+    if (!strcmp(f, "detecting_sweeps")) return (double) b->held.detects;
     if (!strcmp(f, "single_launch_solves")) return (double) b->n_single_launch;
     if (!strcmp(f, "cond_N_active")) return b->pcond_state == 1 ? (double) b->child->N : (double) b->N;
     if (!strcmp(f, "tol_comp_soft_scale")) return b->tol_comp_soft_scale;
@@ -2904,13 +2997,14 @@ struct BlobDesc
     int nf;
     const char *prefix;
     bool masks, read_map;
+    bool matrices; /* the kind carries A / B / Q / R / S: scattering it leaves no stored held-dynamics verdict standing */
 };
-#define GQP_BLOB(fields, prefix, masks, read_map) {fields, (int) (sizeof(fields) / sizeof(fields[0])), prefix, masks, read_map}
+#define GQP_BLOB(fields, prefix, masks, read_map, matrices) {fields, (int) (sizeof(fields) / sizeof(fields[0])), prefix, masks, read_map, matrices}
 static const BlobDesc k_blobs[BLOB_KINDS] = {
-    /* BLOB_IN   */ GQP_BLOB(k_bulk_in_fields, "", true, true),
-    /* BLOB_OUT  */ GQP_BLOB(k_bulk_out_fields, "", false, false),
-    /* BLOB_VEC  */ GQP_BLOB(k_bulk_vec_fields, "", true, false),
-    /* BLOB_SEED */ GQP_BLOB(k_seed_fields, "seed_", false, false),
+    /* BLOB_IN   */ GQP_BLOB(k_bulk_in_fields, "", true, true, true),
+    /* BLOB_OUT  */ GQP_BLOB(k_bulk_out_fields, "", false, false, false),
+    /* BLOB_VEC  */ GQP_BLOB(k_bulk_vec_fields, "", true, false, false),
+    /* BLOB_SEED */ GQP_BLOB(k_seed_fields, "seed_", false, false, false),
 };
 
 /* the public integers: `output` of _bulk_len / _bulk_offset is 0 for the input blob, 2 for its vector part and anything else for
@@ -3104,6 +3198,9 @@ static void bulk_scatter_launch(ocp_qp_gpu_batch *b, const double *src, int len,
  * the kind has mask entries, the launch that turns them into the activity words.  No wait, no timing: those are the caller's */
 static void blob_scatter(ocp_qp_gpu_batch *b, BulkMap &M, const double *src)
 {
+    /* the kinds that carry matrices (BlobDesc::matrices) leave no stored verdict standing */
+    const bool matrices = k_blobs[&M - b->blob].matrices;
+    b->held.data_written(matrices, matrices);
     bulk_scatter_launch(b, src, M.len, M);
     if (M.nm)
         hipLaunchKernelGGL(gqp::k_bulk_masks, dim3((b->B + 63) / 64, (b->N + 1 + GQP_MASK_SPC - 1) / GQP_MASK_SPC), dim3(64), 0, b->stream, src, b->B, M.len, M.d_moff,

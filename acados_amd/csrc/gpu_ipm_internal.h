@@ -59,7 +59,9 @@ struct GqpOpts
                        its step length in GqpDev::apend and the step is applied by k_step_update, a launch of its own (ipm_kernels.hpp) */
     int hold;       /* set by the host loop, read by the one-instance-per-lane box sweeps (ipm_kernels_box.hpp, "held dynamics"): bit 0 --
                        tiles whose counter in GqpDev::tile_inv is full keep [B A]' in registers across the stages; bit 1 -- this launch
-                       (the first affine forward sweep of the root loop) fills the counters.  0 everywhere else */
+                       (the first affine forward sweep of the root loop) fills the counters; bit 2 -- a launch of the held factor
+                       entry (kh_factor) whose packed Hessian was found the same at the stages 0 .. N-1 of every instance: every
+                       stage k < N reads the copy of stage N-1 ("held Hessian").  0 everywhere else */
 };
 
 /* One per-instance HBM array: `E` elements per instance, stored WAVE-TILED,

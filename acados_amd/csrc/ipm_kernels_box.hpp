@@ -319,9 +319,11 @@ struct TileTab
  *   Detection costs no memory traffic: the first affine forward sweep of the root loop (GqpOpts::hold bit 1) fetches every
  * stage's block anyway and compares it, row by row and on the 64-bit patterns, with the one it holds from the stage before
  * (k = 1 .. N-1); the lanes whose stages all agree are counted into GqpDev::tile_inv.  A tile is held when its count equals the
- * instances it carries.  The host zeroes the counters in front of and behind the root loop (gpu_batch.hip, run_ipm): no
- * other launch of these kernels ever sees a flag older than the data.  GqpOpts::hold bit 0 off (option hold_dynamics 0, every
- * sub-level): every tile fetches at every stage.
+ * instances it carries.  The counters are zero outside a root loop (gpu_batch.hip, run_ipm zeroes them behind it).  In front of
+ * the loop the host either zeroes them and lets the loop detect, or -- where nothing has written the arrays behind [B A]' since
+ * the last count (HeldDynamics::ver_dyn, bumped by EVERY writer of those arrays: a new writer must call data_written) -- copies
+ * the stored counters back: no launch of these kernels ever sees a flag older than the data.  GqpOpts::hold bit 0 off (option
+ * hold_dynamics 0, every sub-level): every tile fetches at every stage.
  *   The rhs-only backward sweep has TWO ENTRIES, chosen by the host per launch and not by the kernel per tile.  kb_backrhs fetches
  * the block at every stage; its code is untouched, because a decision inside the kernel was measured twice and cost the tiles that
  * fetch (time-varying dynamics): the block fetched into a carried array under a branch on the tile's flag + 0.04 ms per launch, the
@@ -333,7 +335,8 @@ struct TileTab
  * sub-levels, the tail, sensitivities and hold_dynamics 0 run kb_backrhs.  Scalar "rhs_held_launches" counts its launches.
  *   The factor sweep has the same two entries under the same condition: kb_factor, untouched, and kh_factor behind it (scalar
  * "fact_held_launches").  The host waits for the read-back of the counters alone (an event behind that copy), so the factor
- * launch of the second iteration is already the held one. */
+ * launch of the second iteration is already the held one; a solve that starts from a stored count runs the held entries from its
+ * first launch on. */
 template <int NX, int NU, bool XBOX>
 constexpr bool kb_hold()
 {
@@ -734,7 +737,10 @@ __global__ void __launch_bounds__(64) kh_factor(GqpDev D, GqpOpts O, int redo)
     tiles.template put<KH_COUNT + 1>((double *) D.status);
     tiles.template put<KH_COUNT + 2>(D.stat);
     tiles.template put<KH_COUNT + 3>((double *) (((uint64_t) (unsigned int) D.stat_rows << 32) | (unsigned int) D.stat_inst));
-    /* INVARIANT of every tiles.get(): lanes 0 .. KH_COUNT + 3 of the wave are active (no lane has returned, no divergent branch
+    /* held Hessian (GqpOpts::hold bit 2): the stage whose copy of RSQ every stage k < N reads, -1: each its own.  In the table like
+     * the pointers: a scalar register that lives across the stage loop is one too many here (two spilled) */
+    tiles.template put<KH_COUNT + 4>((double *) (uint64_t) (unsigned int) ((O.hold & 4) ? D.N - 1 : -1));
+    /* INVARIANT of every tiles.get(): lanes 0 .. KH_COUNT + 4 of the wave are active (no lane has returned, no divergent branch
      * is open) -- true from here to the epilogue's reads, because no lane leaves before them and every branch of the stage body is
      * on a wave-uniform value */
 #define KACC(name, e0) acc_tile(tiles.get(KH_##name + zs), (size_t) (e0), i)
@@ -901,7 +907,13 @@ __global__ void __launch_bounds__(64) kh_factor(GqpDev D, GqpOpts O, int redo)
 
         /* ---------------- Hessian rows in load phases: H v, M = H~ + S ---------------- */
         UNROLL for (int r = 0; r < n; r++) hv[r] = 0.0;
-        const Acc aRSQ = KACC(RSQ, k * NP);
+        /* held Hessian (GqpOpts::hold bit 2, the host's choice: k_hess_invariant found RSQ the same at the stages 0 .. N-1 of every
+         * instance): every stage k < N reads the copy of stage N-1 -- the same 64-bit patterns from one block of NP lines per tile that is
+         * read again at every stage and stays on the die, instead of N blocks streamed from HBM.  Stage N reads its own (its
+         * padded input block differs).  The stage is picked in scalar code, from a value derived from the kernel arguments */
+        const int hess_at = (int) (unsigned int) (uint64_t) tiles.get(KH_COUNT + 4);
+        const int kh = (hess_at >= 0 && k < D.N) ? hess_at : k;
+        const Acc aRSQ = KACC(RSQ, kh * NP);
         double H[GQP_HROW_CHUNK * n];
         UNROLL for (int r = 0; r < n; r++)
         {
@@ -1037,6 +1049,30 @@ constexpr auto kh_factor_for() -> void (*)(GqpDev, GqpOpts, int)
 {
     if constexpr (kb_hold<NX, NU, false>() && NX == 8 && NU == 3) return kh_factor<NX, NU>;
     else return nullptr;
+}
+
+/* Held Hessian, the detector: one instance per lane, the packed Hessian of the stages 1 .. N-1 against stage 0's on the 64-bit
+ * patterns (dbits: -0.0 is not +0.0, a NaN pattern compares like any other); cnt[tile] = lanes of the tile whose stages all agree.
+ * Stage N is not compared: its padded input block differs.  One entry at a time is held against its N-1 copies, so that one kernel
+ * serves every shape; it runs once per version of the data (HeldDynamics::hessian_verdict), not per solve.  Lanes past the batch are
+ * not here, finished instances count like any other: the verdict speaks of the data. */
+static __global__ void __launch_bounds__(64) k_hess_invariant(GqpDev D, int *cnt)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D.B) return;
+    const int n = D.NX + D.NU, NP = n * (n + 1) / 2;
+    uint64_t differs = 0;
+    for (int e = 0; e < NP; e++)
+    {
+        const uint64_t first = dbits(GAT(D.RSQ, e));
+        for (int k = 1; k < D.N; k++) differs |= first ^ dbits(GAT(D.RSQ, k * NP + e));
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int same = popc64(__builtin_amdgcn_ballot_w64(differs == 0));
+    if (threadIdx.x == 0) cnt[blockIdx.x] = same;
+#else
+    if (differs == 0) cnt[blockIdx.x] += 1; /* (one lane at a time: the contract is the count, the array is zero before the launch) */
+#endif
 }
 
 /* ------------------------------------------------------- rhs-only backward */
