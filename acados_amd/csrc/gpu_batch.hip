@@ -170,13 +170,19 @@ struct BulkMap
  *   Held Hessian: where every tile is held and the held factor entry exists, hessian_verdict() runs gqp::k_hess_invariant once per
  *   ver_hess and the held factor launches read one copy of RSQ (GqpOpts::hold bit 2) while the verdict is current and positive.
  * Methods: in front of run_ipm. */
+#ifndef GQP_COMPACT_HELD /* (development builds: the other default, for A/B runs of bench.py) */
+#define GQP_COMPACT_HELD 0
+#endif
 struct HeldDynamics
 {
     /* the last solve: scalars "tiles_invariant" (of the solve's own loop, or the stored count it started from), "fact_held_launches"
      * / "rhs_held_launches" (launches of IpmKernels::fact_held / rhs_held, the polish pass's included), "hess_held_launches" (those
      * of fact_held with hold bit 2), "hess_detector_runs", "detecting_sweeps" (1 where the solve's own loop ran the detecting sweep,
-     * 0 where it started from a stored count); reset by ocp_qp_gpu_batch_solve */
+     * 0 where it started from a stored count), "level_held_launches" (those of the held launches above that a dense held level
+     * made, see adopt()), "slim_dyn_copies" / "slim_hess_copies" (hand-overs whose gather of BAt / RSQ read two stage slots per
+     * instance, sub_batch_load); reset by ocp_qp_gpu_batch_solve */
     int tiles_invariant = 0, fact_launches = 0, rhs_launches = 0, hess_launches = 0, hess_detects = 0, detects = 0;
+    int level_launches = 0, slim_dyn = 0, slim_hess = 0;
     hipEvent_t ev = nullptr; /* recorded behind the read-back of the counters */
     /* the data and what is known about it (0 is no version: nothing is known at the start) */
     unsigned ver_dyn = 1, ver_hess = 1;  /* versions of the arrays behind [B A]' and of RSQ */
@@ -189,9 +195,10 @@ struct HeldDynamics
     unsigned pending_ver = 0;            /* ver_dyn at the detecting sweep of this loop; 0: its count is not to be stored */
     bool complete = false;               /* ... every instance was running when that sweep was launched: every wave counted */
     /* the root loop that runs */
-    ocp_qp_gpu_batch *b = nullptr; /* null: a sub-level's record, which does nothing */
+    ocp_qp_gpu_batch *b = nullptr; /* null: a sub-level's record, which does nothing (but see adopt()) */
     bool enabled = false;          /* option hold_dynamics on a one-instance-per-lane box batch */
     bool polish = false;           /* the loop of the polish pass: its count stays its own */
+    bool level = false;            /* the record of a dense held level while its loop runs (adopt()) */
     enum { DETECTING, AWAITING, COUNTED } state = COUNTED;
     int tiles = 0;                 /* full tiles this loop counted */
 
@@ -207,6 +214,13 @@ struct HeldDynamics
      * (one launch, one read-back, one wait for the stream) where ver_hess has moved since the stored verdict */
     bool hessian_verdict(hipStream_t s);
     void end(hipStream_t s);
+    /* the record of a dense level that an all-held root loop made of its survivors (option compact_held): every tile of its `cnt`
+     * slots holds, by the root's count; the Hessian verdict is the root's.  It starts COUNTED, so it never detects, never waits and
+     * never stores a count; its launches are counted into the root's scalars (run_ipm); end() switches it off again */
+    void adopt(ocp_qp_gpu_batch *level, int cnt, bool root_hess_inv);
+    /* the verdicts a hand-over may use WITHOUT asking for one: [B A]' of every instance is stage-invariant / so is RSQ */
+    bool dyn_known() const { return all_held(); }
+    bool hess_known() const { return hess_at == ver_hess && hess_inv; }
     /* a writer of a root batch's matrices: the arrays behind [B A]' (dyn) and / or RSQ (hess) are not what they were */
     void data_written(bool dyn, bool hess) { if (dyn) ver_dyn++; if (hess) ver_hess++; if (!ver_dyn) ver_dyn = 1; if (!ver_hess) ver_hess = 1; }
 };
@@ -316,12 +330,15 @@ struct ocp_qp_gpu_batch
     const KernelSet *force_ks = nullptr; /* sub-batches run the very same kernel set */
     int compact_min = 1 << 30;           /* levels smaller than this are not compacted; off by default: it only
                                             pays once every sweep kernel is bandwidth-bound */
-    int tail_max = 12288;                /* switch to the tail sub-batch when at most this many instances (and 1 / tail_div of the level) remain; 0 = off */
+    int tail_max = 12288;                /* switch to the tail sub-batch when at most this many instances (and 1 / tail_div of the ROOT batch, at every level) remain; 0 = off */
     int tail_div = 4;
     int n_tail_switches = 0;
     /* held dynamics of the one-instance-per-lane box sweeps (ipm_kernels_box.hpp; run_ipm) */
     int hold_dynamics = 1;               /* option: 1 = tiles whose [B A]' is found stage-invariant keep it in registers, 0 = never */
     int hold_hessian = 1;                /* option: 1 = held factor launches read one copy of a stage-invariant RSQ, 0 = every stage its own */
+    int compact_held = GQP_COMPACT_HELD; /* option: 1 = a level of at least compact_held_min instances whose tiles all hold continues in a dense level that
+                                            stays on the held entries once half of it has converged (run_ipm), 0 = never */
+    int compact_held_min = 32768;
     HeldDynamics held;                   /* the protocol of the root loop, what the last solve counted and what is known of the data */
     /* solution sensitivities / factor at the solution */
     bool factor_stale = false;           /* the last solve finished instances on a sub-level: Lf of the root is not theirs */
@@ -1369,6 +1386,8 @@ try
     else if (!strcmp(f, "tail_max")) b->tail_max = *i;
     else if (!strcmp(f, "hold_dynamics")) b->hold_dynamics = *i != 0;
     else if (!strcmp(f, "hold_hessian")) b->hold_hessian = *i != 0;
+    else if (!strcmp(f, "compact_held")) b->compact_held = *i != 0;
+    else if (!strcmp(f, "compact_held_min")) b->compact_held_min = *i;
     else if (!strcmp(f, "tail_div")) b->tail_div = *i < 1 ? 1 : *i;
     else if (!strcmp(f, "solve_max")) b->solve_max = *i;
     else if (!strcmp(f, "cond_N"))
@@ -1782,7 +1801,7 @@ struct Prof
 };
 } /* extern "C++" */
 
-static ocp_qp_gpu_batch *compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, hipStream_t s, SubRole role);
+static ocp_qp_gpu_batch *compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, hipStream_t s, SubRole role, const HeldDynamics *known);
 static void compact_back(ocp_qp_gpu_batch *b, hipStream_t s, SubRole role, int it0);
 static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hipStream_t s, int it, bool polish = false);
 
@@ -1799,7 +1818,10 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
  * iteration after that one on, if EVERY tile of the batch is held, the factor launch and both rhs-only launches go to the entries
  * that hold the block too (IpmKernels::fact_held, gqp::kh_factor; IpmKernels::rhs_held, gqp::kh_backrhs).  They read no flag: a
  * mixed batch, the iteration that detects and every launch outside this loop (sub-levels, tail, sensitivities, ric_alg 0) keep
- * K.fact and K.rhs, which fetch at every stage.  Sub-levels never set either bit and nothing of it is copied by compact_into.
+ * K.fact and K.rhs, which fetch at every stage.  Sub-levels never set either bit and nothing of it is copied by compact_into --
+ * with one exception, the dense held level (option compact_held): a loop whose tiles ALL hold may compact its survivors into a level
+ * that runs the held entries too; that level's record is switched on by HeldDynamics::adopt and off again by end().
+ * What the loop knows of the matrices also shortens its hand-overs (sub_batch_load, "held data").
  */
 /* side -> (stage, activity bit) of k_step_update, once per batch */
 static const int *side_map(ocp_qp_gpu_batch *b)
@@ -1930,6 +1952,19 @@ bool HeldDynamics::hessian_verdict(hipStream_t s)
 void HeldDynamics::end(hipStream_t s)
 {
     if (b) HIPCHK(hipMemsetAsync(b->D.tile_inv, 0, sizeof(int) * (size_t) (b->Bp / 64), s));
+    if (level) enabled = level = false;
+}
+
+void HeldDynamics::adopt(ocp_qp_gpu_batch *lv, int cnt, bool root_hess_inv)
+{
+    b = lv;
+    enabled = level = true;
+    polish = false;
+    pending_ver = 0;
+    state = COUNTED;
+    tiles = (cnt + 63) / 64;
+    hess_at = ver_hess; /* (sub_batch_load has bumped the versions: the verdict is of what it copied) */
+    hess_inv = root_hess_inv;
 }
 
 static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hipStream_t s, int it, bool polish)
@@ -1947,8 +1982,9 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
      * GEN always, box classes up to 16,384 instances from N = 50 on.  ACADOS_AMD_EXT_UPDATE=0 / 1 forces the pass / the launch */
     const char *eext = getenv("ACADOS_AMD_EXT_UPDATE");
     const bool ext_update = b->w16 && (eext ? atoi(eext) != 0 : (b->w16_ng > 0 || (b->B <= 16384 && b->N >= 50)));
-    HeldDynamics none; /* a sub-level takes no part */
-    HeldDynamics &H = top ? root->held : none;
+    HeldDynamics none; /* a sub-level takes no part -- but for the dense level of an all-held root (compact_into: adopt()) */
+    HeldDynamics &H = top ? root->held : b->held.level ? b->held : none;
+    HeldDynamics &Hroot = root->held; /* the scalars of the solve */
     if (top) H.begin(root, s, polish);
     O.hold = H.bits();
     GqpOpts Oc = O; /* options of the corrector-sweep launches */
@@ -1986,8 +2022,9 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         GqpOpts Of = O;
         if (hess_held) Of.hold |= 4;
         prof.timed(1, s, top, [&] { launch_sweep(b, fact_held ? K.fact_held : K.fact, s, D, Of, 0); });
-        if (fact_held) H.fact_launches++;
-        if (hess_held) H.hess_launches++;
+        if (fact_held) Hroot.fact_launches++;
+        if (hess_held) Hroot.hess_launches++;
+        if (fact_held && !top) Hroot.level_launches++;
         root->launches++;
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -2004,11 +2041,15 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
             D.n_perm = nact;
             b->w16_slots = nact;
         }
-        if (!b->wpi && root->tail_max > 0 && nact <= root->tail_max && (long) root->tail_div * nact <= b->B)
+        /* what this loop knows of the matrices goes with a hand-over (sub_batch_load: the slim gather) */
+        const HeldDynamics *known = &H != &none ? &H : nullptr;
+        /* (the tail rule measures the survivors against the ROOT's batch at every level: when the tail takes over, and with it every
+         * output bit, does not depend on whether a level was made in between) */
+        if (!b->wpi && root->tail_max > 0 && nact <= root->tail_max && (long) root->tail_div * nact <= root->B)
         {
             /* the last survivors of a one-instance-per-lane level: a wave that still has ONE active lane pays
              * the full per-wave latency of every sweep, so the tail continues one wave per instance */
-            ocp_qp_gpu_batch *tail = compact_into(b, root, s, SUB_TAIL);
+            ocp_qp_gpu_batch *tail = compact_into(b, root, s, SUB_TAIL, known);
             root->n_tail_switches++;
             run_ipm(tail, root, prof, s, it);
             /* the family's own finalize first: the general one-instance-per-lane kernels refresh the multipliers
@@ -2019,9 +2060,17 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
             compact_back(b, s, SUB_TAIL, it);
             break;
         }
-        if (b->B >= root->compact_min && 2 * nact <= b->B)
+        /* a dense level of the survivors: by size (compact_min, off by default), or -- compact_held -- where every tile of this
+         * loop holds: the level then stays on the held entries (HeldDynamics::adopt) and its hand-over reads two stage slots */
+        const bool held_level = root->compact_held && all_held && b->B >= root->compact_held_min;
+        if ((b->B >= root->compact_min || held_level) && 2 * nact <= b->B)
         {
-            ocp_qp_gpu_batch *level = compact_into(b, root, s, SUB_COMPACT);
+            ocp_qp_gpu_batch *level = compact_into(b, root, s, SUB_COMPACT, known);
+            if (held_level)
+            {
+                level->held.adopt(level, level->B, root->hold_hessian && H.hess_known());
+                hipLaunchKernelGGL(gqp::k_level_held, dim3(level->Bp / 64), dim3(64), 0, s, level->D, level->B);
+            }
             root->n_compactions++;
             run_ipm(level, root, prof, s, it);
             compact_back(b, s, SUB_COMPACT, it);
@@ -2041,7 +2090,8 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
             launch_sweep(b, K.fcorr, s, D, Oc, 1);
             root->launches += 2;
         }
-        if (rhs_held) H.rhs_launches += O.cond_pred_corr ? 2 : 1;
+        if (rhs_held) Hroot.rhs_launches += O.cond_pred_corr ? 2 : 1;
+        if (rhs_held && !top) Hroot.level_launches += O.cond_pred_corr ? 2 : 1;
         if (ext_update)
         {
             /* (behind the redo pair: an instance whose corrector collapsed gets its step length there) */
@@ -2204,13 +2254,36 @@ static void sub_copy(ocp_qp_gpu_batch *b, const SubBatch &sb, const std::vector<
 
 /* QP data, iterate, activity masks and loop scalars of the `cnt` listed instances of b into the first slots of the sub-batch.
  * Returns with the copies done: the caller may reuse its host list, the sub-batch may launch on a stream of its own */
-static void sub_batch_load(ocp_qp_gpu_batch *b, const SubBatch &sb, int cnt, hipStream_t s)
+/* Held data (`known`: the record of the IPM loop that hands over -- the root's, or a dense held level's; `root` takes the tally):
+ * where that record says every tile holds its dynamics, the N stage slots of BAt are N copies of one block, and under a current
+ * positive Hessian verdict so are those of RSQ at the stages 0 .. N-1 -- 50 of the 51 slots of the two arrays that make up three
+ * quarters of an instance's state on C2.  Such an array goes through gqp::k_compact_held, which reads the slots N-1 and N and
+ * writes them all: the same bits as the full copy.  No verdict is asked for the copy's sake; every other caller copies in full */
+static void sub_batch_load(ocp_qp_gpu_batch *b, const SubBatch &sb, int cnt, hipStream_t s, const HeldDynamics *known = nullptr,
+                           ocp_qp_gpu_batch *root = nullptr)
 {
     ocp_qp_gpu_batch *c = sb.c;
     c->B = cnt; /* the sub-batch works on `cnt` slots of its capacity */
     c->D.B = cnt;
-    c->held.data_written(true, true); /* (no sub-batch holds today -- a wave-per-instance family, or a level below the root; kept right all the same) */
-    sub_copy(b, sb, g_state_arrays, cnt, 0, s);
+    c->held.data_written(true, true); /* (a dense held level takes its verdicts from the loop above it, after this: adopt()) */
+    const auto slim_ok = [&](const GArr &big, const GArr &small) {
+        return cnt > 0 && b->N >= 1 && big.p && small.p && big.E == small.E && big.E > 0 && big.E % (b->N + 1) == 0;
+    };
+    const bool slim_dyn = known && root && known->dyn_known() && slim_ok(b->D.BAt, c->D.BAt);
+    const bool slim_hess = known && root && root->hold_hessian && known->hess_known() && slim_ok(b->D.RSQ, c->D.RSQ);
+    for (GqpArrMember m : g_state_arrays)
+    {
+        const GArr &big = b->D.*m, &small = c->D.*m;
+        if ((m == &GqpDev::BAt && slim_dyn) || (m == &GqpDev::RSQ && slim_hess))
+        {
+            /* (up to eight parts share the destination stages of a tile: 51 stage slots are written from one read) */
+            const int chunks = (big.E / (b->N + 1) + 63) / 64, parts = std::min(b->N + 1, 8);
+            GQP_LAUNCH_COOP(gqp::k_compact_held, dim3((cnt + 63) / 64, chunks * parts), dim3(64), 0, s, big, small, sb.d_list, cnt, b->N);
+        }
+        else copy_level(big, small, sb.d_list, cnt, 0, s);
+    }
+    if (slim_dyn) root->held.slim_dyn++;
+    if (slim_hess) root->held.slim_hess++;
     copy_level(b->D.amask, c->D.amask, sb.d_list, cnt, 0, s);
     hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), dim3(64), 0, s, b->D, c->D, sb.d_list, cnt, 0);
     HIPCHK(hipStreamSynchronize(s));
@@ -2224,7 +2297,7 @@ static void sub_batch_store(ocp_qp_gpu_batch *b, const SubBatch &sb, int cnt, Su
         hipLaunchKernelGGL(gqp::k_compact_scalars, dim3((cnt + 63) / 64), dim3(64), 0, s, b->D, sb.c->D, sb.d_list, cnt, 1);
 }
 
-static ocp_qp_gpu_batch *compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, hipStream_t s, SubRole role)
+static ocp_qp_gpu_batch *compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, hipStream_t s, SubRole role, const HeldDynamics *known)
 {
     const bool tail = role == SUB_TAIL;
     SubBatch &sb = b->sub[role];
@@ -2245,7 +2318,7 @@ static ocp_qp_gpu_batch *compact_into(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *roo
     if (!sb.c) sub_batch_create(b, role, tail ? std::max(cnt, std::min(b->tail_max, sb.list_cap)) : std::max(cnt, (b->Bp + 1) / 2));
     ocp_qp_gpu_batch *c = sb.c;
     HIPCHK(hipMemcpyAsync(sb.d_list, list, sizeof(int) * cnt, hipMemcpyHostToDevice, s));
-    sub_batch_load(b, sb, cnt, s); /* (synchronises: `list` (host) must outlive the copy) */
+    sub_batch_load(b, sb, cnt, s, known, root); /* (synchronises: `list` (host) must outlive the copy) */
     *c->h_nact = cnt;
     HIPCHK(hipMemcpyAsync(c->D.n_active, c->h_nact, sizeof(int), hipMemcpyHostToDevice, s));
     /* the level keeps its own statistics rows for its first slots; merged into the parent's table afterwards */
@@ -2431,6 +2504,7 @@ try
     b->n_tail_switches = 0;
     b->n_single_launch = 0;
     b->held.tiles_invariant = b->held.rhs_launches = b->held.fact_launches = b->held.hess_launches = b->held.hess_detects = b->held.detects = 0;
+    b->held.level_launches = b->held.slim_dyn = b->held.slim_hess = 0;
     /* kernel classes: 0 init, 1 back_fact, 2 fwd_aff, 3 back_rhs, 4 fwd_corr, 5 finalize */
     b->prof_cls.clear();
     Prof prof;
@@ -2820,6 +2894,9 @@ try
     if (!strcmp(f, "hess_held_launches")) return (double) b->held.hess_launches;
     if (!strcmp(f, "hess_detector_runs")) return (double) b->held.hess_detects;
     if (!strcmp(f, "detecting_sweeps")) return (double) b->held.detects;
+    if (!strcmp(f, "level_held_launches")) return (double) b->held.level_launches;
+    if (!strcmp(f, "slim_dyn_copies")) return (double) b->held.slim_dyn;
+    if (!strcmp(f, "slim_hess_copies")) return (double) b->held.slim_hess;
     if (!strcmp(f, "single_launch_solves")) return (double) b->n_single_launch;
     if (!strcmp(f, "cond_N_active")) return b->pcond_state == 1 ? (double) b->child->N : (double) b->N;
     if (!strcmp(f, "tol_comp_soft_scale")) return b->tol_comp_soft_scale;

@@ -124,7 +124,7 @@ struct GqpDev
     int *n_active; /* single counter: instances still iterating */
     int *tile_inv; /* [Bp / 64] per 64-instance tile: lanes whose [B A]' is bit for bit the same at every stage k = 0 .. N-1, counted
                       by the first affine forward sweep of the root loop and zero outside that loop (ipm_kernels_box.hpp, "held
-                      dynamics"); sub-levels keep theirs at zero */
+                      dynamics"); sub-levels keep theirs at zero, but for a dense held level (filled by k_level_held while its loop runs) */
     double *stat;  /* [stat_rows][STAT_COLS][Bp_stat] for the first stat_inst instances */
     int stat_inst, stat_rows;
     /* sixteen-lanes-per-instance sweeps: row slot -> instance.  Null: slot = instance.  Otherwise the n_perm instances that

@@ -1422,6 +1422,66 @@ static __global__ void __launch_bounds__(64) k_compact_tile(GArrT<T> big, GArrT<
     }
 }
 
+/* the gather of a per-stage array ([N+1][ES] per instance: BAt, RSQ) whose stage slots 0 .. N-1 are known to be bit for bit the same
+ * in every listed instance (held data: the host's verdicts, HeldDynamics).  Only the source slots N-1 and N are read; EVERY slot of
+ * the destination is written -- k < N from N-1, N from N (the zero slot of BAt, the differently padded last block of RSQ) -- so the
+ * sub-level's arrays are complete and every kernel family runs on them unchanged.  Tiles as in k_compact_tile (64 slots x 64
+ * elements of one stage slot through LDS, either layout on either side); blockIdx.y = chunk of elements + chunks * part, and part p
+ * of gridDim.y / chunks writes the destination stages p, p + parts, ...: the part that reaches stage N loads a second tile. */
+static __global__ void __launch_bounds__(64) k_compact_held(GArr big, GArr small, const int *list, int cnt, int N)
+{
+    __shared__ double tile[64 * 65];
+    const int ES = big.E / (N + 1), chunks = (ES + 63) / 64, parts = gridDim.y / chunks;
+    const int lane = threadIdx.x, s0 = blockIdx.x * 64, e0 = (blockIdx.y % chunks) * 64;
+    const int ns = cnt - s0 < 64 ? cnt - s0 : 64, ne = ES - e0 < 64 ? ES - e0 : 64;
+    int loaded = -1;
+    for (int k = blockIdx.y / chunks; k <= N; k += parts)
+    {
+        const int ksrc = k < N ? N - 1 : N;
+        if (ksrc != loaded) /* (uniform over the block) */
+        {
+            if (loaded >= 0) __syncthreads(); /* the tile has been read by every lane */
+            const int x0 = ksrc * ES + e0;
+            if (big.aos)
+                for (int s = 0; s < ns; s++)
+                {
+                    if (lane < ne) tile[lane * 65 + s] = big.p[(size_t) list[s0 + s] * big.E + x0 + lane];
+                }
+            else if (lane < ns)
+            {
+                const int inst = list[s0 + lane];
+                const double *px = big.p + ((size_t) (inst >> 6) * (size_t) big.E + x0) * 64 + (inst & 63);
+                for (int e = 0; e < ne; e++) tile[e * 65 + lane] = px[(size_t) e * 64];
+            }
+            __syncthreads();
+            loaded = ksrc;
+        }
+        const int y0 = k * ES + e0;
+        if (small.aos)
+            for (int s = 0; s < ns; s++)
+            {
+                if (lane < ne) small.p[(size_t) (s0 + s) * small.E + y0 + lane] = tile[lane * 65 + s];
+            }
+        else if (lane < ns)
+        {
+            const int inst = s0 + lane;
+            double *py = small.p + ((size_t) (inst >> 6) * (size_t) small.E + y0) * 64 + (inst & 63);
+            for (int e = 0; e < ne; e++) py[(size_t) e * 64] = tile[e * 65 + lane];
+        }
+    }
+}
+
+/* a level that runs the held entries (run_ipm, "dense held level"): the counter of every tile of its `cnt` slots is full, and the
+ * slots behind them carry no RUNNING status -- kh_factor keeps its padding lanes alive to the epilogue and decides there by
+ * status[i] alone; a level re-used with fewer survivors would otherwise count a stale slot out of n_active */
+static __global__ void k_level_held(GqpDev D, int cnt)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D.Bp) return;
+    if (i >= cnt) D.status[i] = 0;
+    if ((i & 63) == 0) D.tile_inv[i >> 6] = cnt - i >= 64 ? 64 : cnt - i > 0 ? cnt - i : 0;
+}
+
 static __global__ void k_compact_scalars(GqpDev big, GqpDev small, const int *list, int cnt, int dir)
 {
     const int sidx = blockIdx.x * blockDim.x + threadIdx.x;
