@@ -53,13 +53,6 @@ struct gqp_hip_failure { int code; };
 namespace
 {
 
-#define GQP_WPI_MIN_N 13       /* nu+nx from which the wave-per-instance kernels serve every batch */
-#define GQP_WPI_BATCH_MAX 8192 /* batch size up to which they also serve the smaller stage blocks */
-#define GQP_W16_BATCH_MAX 20480 /* ... where a 16-lanes-per-instance instantiation exists (crossover of the C2 shape: ~20k) */
-#define GQP_WPI_GEN_SMALL_MAX 2048   /* ... for nu + nx <= 6 with general rows / shared slacks (compiled general set) */
-#define GQP_W16_SMALL_MAX 4096       /* ... against the pipelined small-block kernels (nu + nx <= 6) */
-#define GQP_W16_SMALL_XBOX_MAX 12288 /* ... the same with box rows on the states */
-
 /* compiled shape classes; a batch is served by the cheapest one that covers it */
 const KernelSet g_ksets[] = {
     GQP_KSET(4, 1, 0, 0),
@@ -117,10 +110,85 @@ struct PcondzSet
 #define GQP_PCONDZ(NX, NU, BS) {NX, NU, BS, gqp::kz_pcond<NX, NU, BS>, 4 * gqp::PcondzLds<NX, NU, BS>::SZ * sizeof(double), gqp::km_pcond<NX, NU, BS>}
 const PcondzSet g_pcondz_sets[] = {GQP_PCONDZ(8, 3, 5), GQP_PCONDZ(4, 1, 4)};
 
+/* The kernel family of a batch: the answer to DESIGN.md 4's table -- which kernels serve this shape and batch size, on which
+ * mapping of instances to lanes, in which array layout, with how much dynamic LDS per launch kind -- as ONE record.  choose_family()
+ * fills it from the dims and the batch size, family_structure() finishes it once idxb / idxs_rev / idxe are known
+ * (finalize_structure), ric_configure() swaps it for ric_alg 0 and back, a compaction level copies its parent's whole; every reader
+ * (pick_kernels, launch_level, wpi_lds_attributes, the scalars) goes through it.  Both functions stand in front of
+ * batch_create_shape. */
+enum FamilyMap { MAP_LANE, MAP_W16, MAP_WPI }; /* one instance per lane / sixteen lanes per instance / one wave per instance */
+struct FamilyLds /* dynamic LDS bytes per launch kind (one instance per lane: none) */
+{
+    size_t fact = 0;  /* factor sweep (the tile sweep of the small two-rows shapes runs two waves per SIMD: its own, smaller tile) */
+    size_t rhs = 0;   /* rhs sweep; the whole-solve kernel of the sixteen-lanes family */
+    size_t fwd = 0;   /* forward sweeps (wave per instance: one factor buffer instead of two) */
+    size_t whole = 0; /* init and finalize: wave-per-instance kernels in every family but one instance per lane */
+};
+struct Family
+{
+    FamilyMap map = MAP_LANE;
+    int aos = 0;       /* instance-major arrays: every family but one instance per lane */
+    int AW = 1;        /* activity words per stage (64 inequality sides each); 2 only on wave per instance */
+    const KernelSet *compiled = nullptr; /* one instance per lane: the compiled shape class that serves the batch */
+    KernelSet own_ks;  /* every other mapping: the kernel set put together for the padded dims */
+    FamilyLds lds;
+    KernelSet wpi_ks;  /* soft sixteen-lanes family: the wave-per-instance set of the same padded dims and its LDS bytes, what the */
+    FamilyLds wpi_lds; /* batch falls back to if the slack structure is not one-slack-per-row (family_structure) */
+    bool soft = false; /* sixteen lanes: soft box rows (one slack per row) */
+    int ng = 0;        /* ... of the GEN two-rows-per-lane set: general rows per stage it carries (slacks on them too) */
+    int tiles = 0;     /* ... two-rows family: factor sweep on 4 x 4 MFMA tiles (kt_factor) */
+    kern_redo_t solve = nullptr; /* ... whole-solve kernel (batches of at most solve_max instances) */
+    bool mfma = false; /* wave per instance: the factor sweep is the blocked-Cholesky / MFMA kernel (17 <= n <= 32) */
+    bool use_box = false;  /* box-only fast path */
+    int xbox = 0;          /* an inequality row on a state */
+    bool kb_plain = true;  /* one-instance-per-lane box batch: the phase-ordered kernels (false: the pipelined small-block ones) */
+    std::string name;      /* family_name() of the record and the ric_alg it serves */
+
+    bool lane() const { return map == MAP_LANE; }
+    bool w16() const { return map == MAP_W16; }
+    const KernelSet *ks() const { return map == MAP_LANE ? compiled : &own_ks; }
+};
+
+/* The ACADOS_AMD_* switches that steer the family (cross-checks, tests, tools), as family_switches() reads them */
+struct Switch
+{
+    bool set = false;
+    int v = 0;
+    bool off() const { return set && v == 0; }
+    bool on() const { return set && v != 0; }
+};
+struct FamilySwitches
+{
+    Switch wpi, wpi_v1, wpi_batch_max, w16, w16r, w16g, w16t, w16t_gen, wpi_mfma, wpi_mfma_pf, wpi_ct, w16_lds_align; /* choose_family */
+    Switch general_kernels, kb_small; /* family_structure */
+    Switch ext_update, w16_perm;      /* every solve (run_ipm) */
+};
+
+/* what choose_family is told of the dims, and what a caller may pin */
+struct DimsSummary
+{
+    int mx = 0, mu = 0, mg = 0, ms = 0; /* largest nx, nu, ng, ns of a stage */
+    int nct_max = 0;                    /* most inequality sides of a stage, 2 (nb + ng) + 2 ns */
+    bool xbox_dims = false;             /* state bounds after stage 0 */
+};
+struct ForcedChoice
+{
+    int NX = 0, NU = 0;             /* padded dims to match exactly (the condensed batch) */
+    const Family *parent = nullptr; /* a sub-batch: the family of the batch it takes instances from ... */
+    bool wpi = false;               /* ... false: a compaction level, which runs that very family; true: the tail, classical-Riccati
+                                       and sensitivity roles, wave per instance at exactly the parent's padded dims */
+};
+struct FamilyChoice
+{
+    bool ok = false;
+    Family f;
+    std::string refusal; /* !ok: the message */
+};
+
 } // namespace
 
 /* Sub-batches that take instances of a batch over (sub_batch_create / _load / _store below), created on first use:
- * the still-iterating instances in a dense batch of the same kernel set (next level of run_ipm, capacity <= B/2), and three
+ * the still-iterating instances in a dense batch of the same family (next level of run_ipm, capacity <= B/2), and three
  * wave-per-instance batches at the padded dims: the tail for the last survivors of a one-instance-per-lane level, the one every
  * ric_alg 0 solve of such a batch is handed to, the one its sensitivities run in slice by slice.  (The condensed batch `child` of
  * partial condensing is a different QP, not a subset of the instances: not one of them) */
@@ -232,30 +300,11 @@ struct ocp_qp_gpu_batch
     std::vector<std::vector<int>> idxb, idxs_rev, idxe; /* as given (original row order) */
     std::vector<std::vector<int>> perm;                   /* original box row -> sorted row */
     bool finalized = false;
-    bool use_box = false; /* box-only fast path */
-    int aos = 0;          /* instance-major arrays: wave-per-instance kernel family */
-    int AW = 1;           /* activity words per stage (64 inequality sides each); 2 only for wave-per-instance batches */
-    int wpi = 0;          /* wave-per-instance kernels (ipm_kernels_wpi.hpp): one workgroup per instance */
-    bool wpi_mfma = false; /* ... whose factor sweep is the blocked-Cholesky / MFMA kernel (17 <= n <= 32) */
-    int w16 = 0;          /* ... whose four sweeps are the 16-lanes-per-instance kernels (ipm_kernels_w16.hpp): 4 instances per workgroup */
-    size_t shmem = 0;     /* their dynamic LDS bytes (rhs sweep, init, finalize) */
-    size_t shmem_fwd = 0; /* ... of the forward sweeps (one factor buffer instead of two) */
-    size_t shmem_fact = 0; /* dynamic LDS bytes of the factor sweep */
-    bool w16_soft = false; /* ... with soft box rows (one slack per row) */
-    int w16_ng = 0;        /* ... of the GEN two-rows-per-lane set: general rows per stage it carries (slacks on them too) */
-    KernelSet wpi_ks;      /* the wave-per-instance set of the same padded dims (fallback of w16_soft) */
+    Family fam;            /* the kernel family that serves the batch (choose_family, family_structure, ric_configure) */
     int w16_slots = 0;     /* row slots a sweep launch covers: B, or the live instances once GqpDev::perm lists them */
-    size_t w16_shmem = 0;  /* dynamic LDS bytes of a 16-lanes-per-instance workgroup (4 instances) */
-    size_t w16_shmem_fact = 0; /* ... of the factor sweep (the tile sweep of the small two-rows shapes runs two waves per SIMD: its own, smaller tile) */
-    int w16_tiles = 0;     /* two-rows family: factor sweep on 4 x 4 MFMA tiles (kt_factor) */
     int *d_side_map = nullptr; /* k_step_update: side -> stage * 128 + activity bit (-1: equality-flagged row), built on first use */
-    kern_redo_t w16_solve = nullptr; /* whole-solve kernel of the family (batches of at most solve_max instances) */
     int solve_max = 256;   /* largest batch that is solved in one launch (option "solve_max", 0 = off) */
     int n_single_launch = 0;
-    KernelSet own_ks;     /* runtime-shaped kernel set of a wpi batch (ks points here) */
-    int xbox = 0;
-    const KernelSet *ks = nullptr;
-    std::string kname;
     std::vector<GqpStage> st;
     GqpStage *d_st = nullptr;
     GqpDev D = {};
@@ -302,7 +351,6 @@ struct ocp_qp_gpu_batch
     int print_level = 0;
     double t0_min = 1e-16, lam0_min = 1e-16; /* lower clips of t / lam at a hot start (HPIPM args of the same name) */
     int profile = 0;                 /* per-kernel-class HIP event timing on the launch stream */
-    bool kb_plain = true;            /* one-instance-per-lane box batch: the phase-ordered kernels (false: the pipelined small-block ones) */
     int stream_priority = 0;         /* HIP stream priority of this batch and of the sub-batches it creates (0: default) */
     std::vector<hipEvent_t> prof_ev; /* pool, pairs (start, stop) */
     std::vector<int> prof_cls;       /* kernel class of each recorded pair */
@@ -312,7 +360,6 @@ struct ocp_qp_gpu_batch
     /* partial condensing (pcond_kernels.hpp) */
     int cond_N = 0;                 /* requested N2; 0 or N = full space */
     int cond_keep_iterate = 0;      /* hot start of a condensed solve from the child's own last iterate (not from the root's) */
-    int force_NX = 0, force_NU = 0; /* child batches are pinned to the kernel shape the condense kernel writes */
     std::vector<int> user_blocks;   /* cond_block_size (N2 entries) or empty: N/N2 each, remainder to the first blocks */
     int pcond_state = 0;            /* 0 unchecked, 1 active, -1 not applicable (message printed once) */
     ocp_qp_gpu_batch *child = nullptr;
@@ -327,7 +374,6 @@ struct ocp_qp_gpu_batch
     double time_xcond = 0.0;
     bool lhs_ready = false;         /* condense_lhs done: the next solve only condenses the vector part */
     SubBatch sub[SUB_ROLES];
-    const KernelSet *force_ks = nullptr; /* sub-batches run the very same kernel set */
     int compact_min = 1 << 30;           /* levels smaller than this are not compacted; off by default: it only
                                             pays once every sweep kernel is bandwidth-bound */
     int tail_max = 12288;                /* switch to the tail sub-batch when at most this many instances (and 1 / tail_div of the ROOT batch, at every level) remain; 0 = off */
@@ -346,19 +392,11 @@ struct ocp_qp_gpu_batch
     GArr sfix = {nullptr, 0, 0};         /* derivative of the equality-flagged variables (e.g. x0), [N+2][n] */
     int *d_saved_status = nullptr;
     /* Riccati recursion (option "ric_alg"): 1 square-root (every family), 0 classical (wave-per-instance sweeps only, RIC0 of
-     * ipm_kernels_wpi.hpp).  A wave-per-instance-layout batch swaps its kernel set in place (ric1 keeps what it replaced); a
+     * ipm_kernels_wpi.hpp).  A wave-per-instance-layout batch swaps its family in place (ric1_fam keeps what it replaced); a
      * one-instance-per-lane batch hands every solve to sub[SUB_RIC0], a wave-per-instance batch at its padded dims */
     int ric_alg = 1;
-    struct Ric1
-    {
-        bool saved = false;
-        KernelSet own_ks;
-        int w16 = 0;
-        kern_redo_t w16_solve = nullptr;
-        bool wpi_mfma = false;
-        size_t shmem = 0, shmem_fwd = 0, shmem_fact = 0;
-        std::string kname;
-    } ric1;
+    Family ric1_fam;         /* ... the family ric_alg 1 runs on, kept while ric_alg 0 is on (ric_configure) */
+    bool ric1_saved = false;
     int n_compactions = 0;
     /* KKT residuals of the current (data, iterate) on demand (res_kernels.hpp) */
     gqp::ResOut R = {{nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, nullptr, 0};
@@ -399,7 +437,7 @@ template <class T>
 GArrT<T> garr(ocp_qp_gpu_batch *b, size_t E)
 {
     GArrT<T> a;
-    a.aos = b->aos;
+    a.aos = b->fam.aos;
     a.E = (int) (E ? E : 1);
     a.p = dalloc<T>(b, (size_t) a.E * (size_t) b->Bp);
     return a;
@@ -437,7 +475,7 @@ GqpOpts effective_opts(const GqpOpts &o, const ocp_qp_gpu_batch *b)
 int padded_var(const ocp_qp_gpu_batch *b, int k, int iv)
 {
     /* index in [u(nu_k); x(nx_k)] -> index in padded [u(NU); x(NX)] */
-    return iv < b->nu[k] ? iv : b->ks->NU + (iv - b->nu[k]);
+    return iv < b->nu[k] ? iv : b->fam.ks()->NU + (iv - b->nu[k]);
 }
 
 /* the classical Riccati kernel set of the wave-per-instance family at padded dims (wx, wu) */
@@ -462,66 +500,354 @@ KernelSet wpi_ric0_set(int wx, int wu, int mg, int ms)
     return KernelSet{wx, wu, mg, ms, init, fact, rhs, faff, fcor, fin, {{fact, fact}, {rhs, rhs}, {faff, faff}, {fcor, fcor}}, fin};
 }
 
+/* ---- the kernel family of a batch: DESIGN.md 4's table in code ---- */
+
+FamilySwitches family_switches()
+{
+    FamilySwitches sw;
+    const struct { const char *name; Switch FamilySwitches::*m; } all[] = {
+        {"ACADOS_AMD_WPI", &FamilySwitches::wpi}, {"ACADOS_AMD_WPI_V1", &FamilySwitches::wpi_v1},
+        {"ACADOS_AMD_WPI_BATCH_MAX", &FamilySwitches::wpi_batch_max}, {"ACADOS_AMD_W16", &FamilySwitches::w16},
+        {"ACADOS_AMD_W16R", &FamilySwitches::w16r}, {"ACADOS_AMD_W16G", &FamilySwitches::w16g},
+        {"ACADOS_AMD_W16T", &FamilySwitches::w16t}, {"ACADOS_AMD_W16T_GEN", &FamilySwitches::w16t_gen},
+        {"ACADOS_AMD_WPI_MFMA", &FamilySwitches::wpi_mfma}, {"ACADOS_AMD_WPI_MFMA_PF", &FamilySwitches::wpi_mfma_pf},
+        {"ACADOS_AMD_WPI_CT", &FamilySwitches::wpi_ct}, {"ACADOS_AMD_W16_LDS_ALIGN", &FamilySwitches::w16_lds_align},
+        {"ACADOS_AMD_GENERAL_KERNELS", &FamilySwitches::general_kernels}, {"ACADOS_AMD_KB_SMALL", &FamilySwitches::kb_small},
+        {"ACADOS_AMD_EXT_UPDATE", &FamilySwitches::ext_update}, {"ACADOS_AMD_W16_PERM", &FamilySwitches::w16_perm}};
+    for (const auto &e : all)
+        if (const char *v = getenv(e.name)) { (sw.*e.m).set = true; (sw.*e.m).v = atoi(v); }
+    return sw;
+}
+
+/* the family of the classical Riccati recursion at the padded dims of f: the RIC0 kernels of the wave-per-instance family.  What a
+ * wave-per-instance-layout batch runs on while ric_alg is 0, and what a one-instance-per-lane batch hands its solves to */
+Family ric0_family(const Family &f)
+{
+    const int wx = f.ks()->NX, wu = f.ks()->NU, mg = f.ks()->NG, ms = f.ks()->NS;
+    const size_t con = gqp::wpi_con_doubles(wx + wu, mg, ms);
+    Family r = f;
+    r.map = MAP_WPI;
+    r.own_ks = wpi_ric0_set(wx, wu, mg, ms);
+    r.solve = nullptr;
+    r.mfma = false;
+    r.lds.rhs = r.lds.whole = (gqp::wpi3_lds_doubles(wx, wu) + con) * sizeof(double);
+    r.lds.fwd = (gqp::wpi3_lds_doubles(wx, wu, 1) + con) * sizeof(double);
+    r.lds.fact = (gqp::wpi2_ric0_lds_doubles(wx, wu) + con) * sizeof(double);
+    return r;
+}
+
+/* the kernel name of a family as ocp_qp_gpu_batch_kernel_name reports it; ric_alg 0: of what the solves then run on */
+std::string family_name(const Family &f, int ric_alg)
+{
+    if (ric_alg == 0 && f.lane()) return family_name(ric0_family(f), 0);
+    const KernelSet &k = *f.ks();
+    char nm[160];
+    if (f.w16() && f.ng) snprintf(nm, sizeof(nm), "w16r-gen<NX=%d,NU=%d,NG=%d>", k.NX, k.NU, f.ng);
+    else if (f.w16()) snprintf(nm, sizeof(nm), f.soft ? "w16-soft<NX=%d,NU=%d>" : k.NX + k.NU > 16 ? "w16r-box<NX=%d,NU=%d>" : "w16-box<NX=%d,NU=%d>", k.NX, k.NU);
+    else if (!f.lane())
+    {
+        const char *tag = f.mfma ? ",mfma" : ric_alg == 0 ? ",ric0" : "";
+        if (k.NG || k.NS) snprintf(nm, sizeof(nm), "wpi-gen(nx=%d,nu=%d,ng=%d,ns=%d,lds=%zuB%s)", k.NX, k.NU, k.NG, k.NS, f.lds.fact, tag);
+        else snprintf(nm, sizeof(nm), "wpi-box(nx=%d,nu=%d,lds=%zuB%s)", k.NX, k.NU, f.mfma ? f.lds.fact : f.lds.rhs, tag);
+    }
+    else if (f.use_box) snprintf(nm, sizeof(nm), "1tpi-%s<NX=%d,NU=%d,XBOX=%d>", f.kb_plain ? "box" : "pipe", k.NX, k.NU, f.xbox);
+    else snprintf(nm, sizeof(nm), "1tpi<NX=%d,NU=%d,NG=%d,NS=%d>", k.NX, k.NU, k.NG, k.NS);
+    return nm;
+}
+
+/* batch thresholds of the table (measured crossovers; the rules that use them are in choose_family) */
+#define GQP_WPI_MIN_N 13       /* nu+nx from which the wave-per-instance kernels serve every batch */
+#define GQP_WPI_BATCH_MAX 8192 /* batch size up to which they also serve the smaller stage blocks */
+#define GQP_W16_BATCH_MAX 20480 /* ... where a 16-lanes-per-instance instantiation exists (crossover of the C2 shape: ~20k) */
+#define GQP_WPI_GEN_SMALL_MAX 2048   /* ... for nu + nx <= 6 with general rows / shared slacks (compiled general set) */
+#define GQP_W16_SMALL_MAX 4096       /* ... against the pipelined small-block kernels (nu + nx <= 6) */
+#define GQP_W16_SMALL_XBOX_MAX 12288 /* ... the same with box rows on the states */
+
+/* Which family serves a batch of n_batch instances with these dims: the table of DESIGN.md 4.  No HIP call, no allocation, nothing
+ * of a batch is touched; a refusal comes back with its message.  The switches are the cross-checks of the tests and tools. */
+FamilyChoice choose_family(const DimsSummary &d, int n_batch, const ForcedChoice &forced, const FamilySwitches &sw)
+{
+    FamilyChoice out;
+    Family &f = out.f;
+    const int mx = d.mx, mu = d.mu, mg = d.mg, ms = d.ms;
+    /* inequality sides per stage: 64 per activity word; the one-instance-per-lane kernels read one word, the
+     * wave-per-instance ones up to two */
+    if (d.nct_max > 128)
+    {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "acados_amd: a stage has %d inequality sides (2(nb+ng)+2ns > 128): unsupported\n", d.nct_max);
+        out.refusal = msg;
+        return out;
+    }
+    if (forced.parent && !forced.wpi) /* a compaction level runs the very family of its parent */
+    {
+        f = *forced.parent;
+        out.ok = true;
+        return out;
+    }
+    /* padded dims to match exactly: the ones given, or the parent's for its wave-per-instance sub-batches */
+    const int force_NX = forced.wpi ? forced.parent->ks()->NX : forced.NX, force_NU = forced.wpi ? forced.parent->ks()->NU : forced.NU;
+    /* compiled shape classes: a batch is served by the cheapest one that covers it */
+    const KernelSet *lane = nullptr;
+    double best = 1e300;
+    auto consider = [&](const KernelSet &ks) {
+        if (ks.NX < mx || ks.NU < mu || ks.NG < mg || ks.NS < ms) return;
+        if (force_NX && (ks.NX != force_NX || ks.NU != force_NU || ks.NG || ks.NS)) return;
+        const double n = ks.NX + ks.NU;
+        const double cost = n * n * n + 10.0 * (ks.NG + ks.NS) * n * n;
+        if (cost < best) { best = cost; lane = &ks; }
+    };
+    for (const KernelSet &ks : g_ksets) consider(ks);
+    /* the rolled-loop / scratch-resident instantiations only serve as a cross-check of the wave-per-instance
+     * family (ACADOS_AMD_WPI=0); by default a shape no register-resident instantiation covers goes there */
+    if (sw.wpi.off())
+        for (int q = 0; q < g_n_ksets_large; q++) consider(g_ksets_large[q]);
+    if (forced.parent) lane = forced.parent->ks();
+    /* wave-per-instance family (ipm_kernels_wpi.hpp): box-constrained QPs whose stage block is too large for
+     * the one-instance-per-lane register mapping.  Dimensions are runtime values there: no padding to a
+     * compiled shape.  ACADOS_AMD_WPI=0/1 overrides the size rule (tests). */
+    const bool need_wpi = d.nct_max > 64;
+    if (need_wpi) lane = nullptr; /* no one-instance-per-lane kernel may serve it */
+    int wx = force_NX ? force_NX : mx, wu = force_NU ? force_NU : mu;
+    const bool gen = mg > 0 || ms > 0;
+    const bool ref = sw.wpi_v1.on() && !gen;
+    /* sixteen lanes per instance: the smallest compiled shape that covers the dims (per-stage dims live inside
+     * the padded shape); a sub-level created for a hand-over must match its parent's padded dims exactly */
+    const bool soft_dims = mg == 0 && ms > 0; /* slacks on box rows only: the SOFT variants, if the structure allows */
+    const W16Set *w16 = nullptr;
+    if (!need_wpi && !ref && !sw.w16.off())
+        for (const W16Set &ws : g_w16_sets)
+        {
+            bool fits = force_NX ? (ws.NX == wx && ws.NU == wu) : (ws.NX >= wx && ws.NU >= wu);
+            if (!gen) fits = fits && ws.fact && ws.NG == 0;
+            else if (soft_dims) fits = fits && ws.sfact && ws.NG == 0;                       /* slacks on box rows only */
+            /* general rows (a small block with a compiled one-instance-per-lane general set -- the golden shared-slack
+             * structure, nx = 4, nu = 1 -- keeps the dispatch it was measured with: gen_small below) */
+            else fits = fits && ws.sfact && ws.NG >= mg && !sw.w16g.off() && !(lane && lane->NX + lane->NU <= 6);
+            if (ws.NX + ws.NU > 16 && sw.w16r.off()) fits = false;
+            /* two rows per lane: dims run PADDED inside the compiled shape, so its ~2.3x over the wave-per-instance
+             * kernels (which take dims at run time) is gone once the padded block has more than twice the work:
+             * the shape must cover at least 77 % of the compiled nu + nx */
+            if (ws.NX + ws.NU > 16 && !force_NX && 13 * (wx + wu) < 10 * (ws.NX + ws.NU)) fits = false;
+            if (fits && (!w16 || ws.NX + ws.NU < w16->NX + w16->NU)) w16 = &ws;
+        }
+    const bool has_w16 = w16 != nullptr;
+    /* size rule: large stage blocks always; small ones while the batch is too small to fill the chip with 64
+     * instances per wave (measured crossover on the C2 shape between 4,096 and 16,384 instances,
+     * tools/family_crossover.py).  ACADOS_AMD_WPI_BATCH_MAX overrides the batch threshold. */
+    /* state bounds after stage 0 (the mass-spring class, DimsSummary::xbox_dims): the one-instance-per-lane kernels of that class
+     * run out of registers, the sixteen-lanes kernels win at every batch size measured (tools/xbox_rate.py) */
+    /* nu + nx <= 6: the pipelined one-instance-per-lane kernels (ipm_kernels_box_small.hpp) take over much earlier
+     * -- measured crossover on nx = 4, nu = 1 between 2,048 and 4,096 instances (N = 100; 4,096 ... 7,281 at N = 20),
+     * with bounds on every state between 7,281 and 16,384; at 65,536 they are 2.7-2.9x (1.4x) ahead
+     * (tools/small_shape_crossover.py) */
+    const bool kb_small = !gen && lane && lane->NX + lane->NU <= 6;
+    /* general rows / shared slacks on a small block with a compiled one-instance-per-lane set (the reference's golden
+     * structure pend_idxs_rev_min_qp0: nx = 4, nu = 1, two general rows sharing one slack): 1,024 instances 3.45 ms
+     * there against 2.65 ms on the wave-per-instance kernels, 8,192: 4.4 against 9.2 ms, 65,536: 8.4 against 74 ms */
+    const bool gen_small = gen && lane && lane->NX + lane->NU <= 6;
+    const int batch_max = sw.wpi_batch_max.set ? sw.wpi_batch_max.v
+                        : !has_w16 ? (gen_small ? GQP_WPI_GEN_SMALL_MAX : GQP_WPI_BATCH_MAX)
+                        : kb_small ? (d.xbox_dims ? GQP_W16_SMALL_XBOX_MAX : GQP_W16_SMALL_MAX)
+                        /* general rows / slacks on the sixteen-lanes GEN kernels: the one-instance-per-lane alternative is the
+                         * general set of a (much) larger padded shape with its blocks in scratch -- never */
+                        : (d.xbox_dims || (gen && !soft_dims && !gen_small) ? INT_MAX : GQP_W16_BATCH_MAX);
+    /* (a shape no compiled one-instance-per-lane set covers runs here whatever the override says) */
+    const bool want = forced.wpi || need_wpi || !lane || (sw.wpi.set ? sw.wpi.v != 0 : (wx + wu >= GQP_WPI_MIN_N || n_batch <= batch_max));
+    if (want && wx + wu <= 64 && wx >= 1 && mg <= 32 && ms <= 32)
+    {
+        if (w16) { wx = w16->NX; wu = w16->NU; }
+        /* factor sweep: register-tile kernel for the tile count of this shape; rhs-only and forward sweeps on
+         * the packed factor; GEN variants carry general constraints and slacks.  ACADOS_AMD_WPI_V1=1 selects
+         * the plain LDS-resident reference kernels of the family (box-constrained QPs only), kept for
+         * cross-checking. */
+        static const kern_redo_t fact_box[8] = {gqp::kw_factor<1, false>, gqp::kw_factor<2, false>, gqp::kw_factor<3, false>,
+                                                gqp::kw_factor<4, false>, gqp::kw_factor<5, false>, gqp::kw_factor<6, false>,
+                                                gqp::kw_factor<7, false>, gqp::kw_factor<8, false>};
+        static const kern_redo_t fact_gen[8] = {gqp::kw_factor<1, true>, gqp::kw_factor<2, true>, gqp::kw_factor<3, true>,
+                                                gqp::kw_factor<4, true>, gqp::kw_factor<5, true>, gqp::kw_factor<6, true>,
+                                                gqp::kw_factor<7, true>, gqp::kw_factor<8, true>};
+        const int t8 = (wx + wu + 7) / 8 - 1;
+        /* 17 <= n <= 32: blocked Cholesky + the O(n^3) parts on the FP64 matrix pipe (ipm_kernels_wpi_mfma.hpp).
+         * Measured (tools/factor_variants.py, 4,096 instances): C4 class 3.97 vs 4.10 ms per factor launch, box class
+         * nx=24 nu=6 2.40 vs 2.07 ms, condensed C3 shape 0.35 vs 0.33 ms -- the FP64 matrix pipe is slower than the
+         * vector pipe on this chip (tools/mfma_f64_probe), so it serves the class it helps (general rows + slacks) by
+         * default; ACADOS_AMD_WPI_MFMA=1 / 0 forces it on / off for every shape in range */
+        const bool mfma = !ref && !w16 && wx + wu > 16 && wx + wu <= 32 && (sw.wpi_mfma.set ? sw.wpi_mfma.v != 0 : gen);
+        kern_redo_t fact_ct = nullptr, rhs_ct = nullptr, faff_ct = nullptr, fcor_ct = nullptr;
+        /* compile-time dims where they pay: the condensed C3 shape (nx=8 nu=15, box): factor sweep 0.328 -> 0.287 ms
+         * per 4,096 launch.  Measured and NOT kept: nx=24 nu=3 general (4.09 -> 5.13 ms) and nx=24 nu=6 box (2.07 ->
+         * 2.15 ms) -- full unrolling costs those shapes more in registers than the folded arithmetic saves
+         * (tools/factor_variants.py).  ACADOS_AMD_WPI_CT=0 keeps the run-time-shaped instantiations */
+        if (!ref && !w16 && !sw.wpi_ct.off())
+        {
+#define GQP_CT(GENV, X, U, T)                                                                                     \
+    if (gen == GENV && wx == X && wu == U)                                                                        \
+    {                                                                                                             \
+        fact_ct = gqp::kw_factor<T, GENV, X, U>; rhs_ct = gqp::kw_backrhs<GENV, X, U>;                               \
+        faff_ct = gqp::kw_fwd<false, GENV, X, U>; fcor_ct = gqp::kw_fwd<true, GENV, X, U>;                             \
+    }
+            GQP_CT(false, 8, 15, 3)
+#undef GQP_CT
+        }
+        static const kern_redo_t fact_mf[2][3] = {{gqp::kw_factor_m<false, 0>, gqp::kw_factor_m<false, 1>, gqp::kw_factor_m<false, 2>},
+                                                  {gqp::kw_factor_m<true, 0>, gqp::kw_factor_m<true, 1>, gqp::kw_factor_m<true, 2>}};
+        const int pf = sw.wpi_mfma_pf.set ? std::max(0, std::min(2, sw.wpi_mfma_pf.v)) : 0; /* register prefetch did not pay (VGPR pressure) */
+        const kern_redo_t fact = ref ? gqp::kw_backward<true> : mfma ? fact_mf[gen ? 1 : 0][pf] : fact_ct ? fact_ct : gen ? fact_gen[t8] : fact_box[t8];
+        kern_redo_t rhs = ref ? gqp::kw_backward<false> : gen ? gqp::kw_backrhs<true> : gqp::kw_backrhs<false>;
+        kern_redo_t faff = ref ? gqp::kw_forward<false> : gen ? gqp::kw_fwd<false, true> : gqp::kw_fwd<false, false>;
+        kern_redo_t fcor = ref ? gqp::kw_forward<true> : gen ? gqp::kw_fwd<true, true> : gqp::kw_fwd<true, false>;
+        if (rhs_ct) { rhs = rhs_ct; faff = faff_ct; fcor = fcor_ct; }
+
+        const kern_opts_t init = gen ? gqp::kw_init<true> : gqp::kw_init<false>;
+        const kern_plain_t fin = gen ? gqp::kw_finalize<true> : gqp::kw_finalize<false>;
+        f.own_ks = KernelSet{wx, wu, mg, ms, init, fact, rhs, faff, fcor, fin,
+                             {{fact, fact}, {rhs, rhs}, {faff, faff}, {fcor, fcor}}, fin};
+        f.map = MAP_WPI;
+        f.mfma = mfma;
+        f.aos = 1;
+        f.AW = need_wpi ? 2 : 1;
+        const size_t con = gqp::wpi_con_doubles(wx + wu, mg, ms);
+        f.lds.rhs = f.lds.whole = (ref ? gqp::wpi_lds_doubles(wx, wu) : gqp::wpi3_lds_doubles(wx, wu) + con) * sizeof(double);
+        f.lds.fwd = (ref ? gqp::wpi_lds_doubles(wx, wu) : gqp::wpi3_lds_doubles(wx, wu, 1) + con) * sizeof(double);
+        f.lds.fact = (ref ? gqp::wpi_lds_doubles(wx, wu) : (mfma ? gqp::wpim_lds_doubles(wx, wu) : gqp::wpi2_lds_doubles(wx, wu)) + con) * sizeof(double);
+        /* small box-constrained stage blocks: four instances per wave, register rows + DPP row broadcasts */
+        if (w16)
+        {
+            const W16Set &ws = *w16;
+            f.wpi_ks = f.own_ks; /* what the batch falls back to if the slack structure is not one-slack-per-box-row */
+            f.wpi_lds = f.lds;
+            /* ACADOS_AMD_W16T=0: the factor sweep of the two-rows family on register rows (ky_factor); _W16T_GEN=0: of the GEN
+             * instantiations alone */
+            const bool tiles = ws.tfact && !sw.w16t.off() && !(gen && sw.w16t_gen.off());
+            const kern_redo_t kf = tiles ? ws.tfact : (gen ? ws.sfact : ws.fact), kr = gen ? ws.srhs : ws.rhs;
+            const kern_redo_t ka = gen ? ws.sfaff : ws.faff, kc = gen ? ws.sfcor : ws.fcor;
+            f.own_ks.back_fact = kf; f.own_ks.back_rhs = kr; f.own_ks.fwd_aff = ka; f.own_ks.fwd_corr = kc;
+            for (int q = 0; q < 2; q++)
+            {
+                f.own_ks.box.fact[q] = kf; f.own_ks.box.rhs[q] = kr;
+                f.own_ks.box.fwd_aff[q] = ka; f.own_ks.box.fwd_corr[q] = kc;
+            }
+            f.map = MAP_W16;
+            f.soft = gen;
+            f.ng = ws.NG;
+            f.tiles = tiles;
+            f.solve = gen ? ws.ssolve : ws.solve;
+            f.lds.rhs = f.lds.fwd = ws.shmem; /* (init and finalize stay the wave-per-instance kernels: lds.whole) */
+            f.lds.fact = tiles ? ws.tshmem : ws.shmem;
+            if (sw.w16_lds_align.set && sw.w16_lds_align.v > 1) /* development: allocation rounded up / padded */
+            {
+                const size_t a = (size_t) sw.w16_lds_align.v;
+                f.lds.rhs = f.lds.fwd = (f.lds.rhs + a - 1) / a * a;
+                f.lds.fact = (f.lds.fact + a - 1) / a * a;
+            }
+        }
+    }
+    if (f.lane())
+    {
+        if (!lane)
+        {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "acados_amd: no kernel instantiation covers nx<=%d nu<=%d ng<=%d ns<=%d\n", mx, mu, mg, ms);
+            out.refusal = msg;
+            return out;
+        }
+        f.compiled = lane;
+    }
+    f.name = family_name(f, 1);
+    out.ok = true;
+    return out;
+}
+
+/* The second step, once the structure is known (finalize_structure): st as built there from idxb / idxs_rev / idxe, the slack
+ * references and the equality flags themselves.  The SOFT sixteen-lanes family falls back to wave per instance where a slack is
+ * shared; box-only fast path, box rows on states, the pipelined small-block kernels. */
+void family_structure(Family &f, const std::vector<GqpStage> &st, const std::vector<std::vector<int>> &idxs_rev,
+                      const std::vector<std::vector<int>> &idxe, const FamilySwitches &sw)
+{
+    const int NX = f.ks()->NX, NU = f.ks()->NU;
+    if (f.w16() && f.soft)
+    {
+        /* the SOFT sixteen-lanes kernels eliminate a slack inside the lane that owns its row: every slack must belong
+         * to exactly one box row that is not an equality-flagged one; anything else runs on the general
+         * wave-per-instance kernels of the same padded dims */
+        bool ok = true;
+        for (size_t k = 0; k < st.size() && ok; k++)
+        {
+            const GqpStage &S = st[k];
+            std::vector<int> refs(S.ns, 0);
+            for (int r = 0; r < S.nb + (f.ng ? S.ng : 0); r++)
+                if (S.srev[r] >= 0) refs[S.srev[r]]++;
+            for (int q = 0; q < S.ns; q++) ok = ok && refs[q] == 1;
+            if (!f.ng) ok = ok && S.ng == 0;
+            else ok = ok && __builtin_popcountll(S.bmask & ~S.emask) + S.ng <= 16; /* GEN: one inequality row per lane */
+            for (size_t e = 0; e < idxe[k].size(); e++) ok = ok && idxs_rev[k][idxe[k][e]] < 0;
+        }
+        if (!ok)
+        {
+            f.map = MAP_WPI;
+            f.own_ks = f.wpi_ks;
+            f.lds = f.wpi_lds;
+            f.solve = nullptr;
+            f.soft = false;
+            f.tiles = 0;
+        }
+    }
+    int o_g = 0, o_s = 0;
+    f.xbox = 0;
+    for (const GqpStage &S : st)
+    {
+        o_g += S.ng; o_s += S.ns;
+        if (((S.bmask & ~S.emask) >> NU) != 0) f.xbox = 1;
+    }
+    /* ACADOS_AMD_GENERAL_KERNELS (any value): the general sweeps for a box-only batch (cross-check) */
+    f.use_box = !f.lane() || (o_g == 0 && o_s == 0 && !sw.general_kernels.set);
+    /* nu + nx <= 6: the pipelined kernels of ipm_kernels_box_small.hpp ("1tpi-pipe"); ACADOS_AMD_KB_SMALL=0 keeps the
+     * phase-ordered ones of ipm_kernels_box.hpp (cross-check) */
+    if (f.use_box && f.lane()) f.kb_plain = sw.kb_small.off() || NX + NU > 6;
+    f.name = family_name(f, 1);
+}
+
 /* dynamic LDS above the default limit: raise it for the four sweep kernels of the batch's own set */
 static void wpi_lds_attributes(ocp_qp_gpu_batch *b)
 {
-    if (std::max(b->shmem, b->shmem_fact) <= 64 * 1024) return;
-    const void *fns[] = {(const void *) b->own_ks.back_fact, (const void *) b->own_ks.back_rhs,
-                         (const void *) b->own_ks.fwd_aff, (const void *) b->own_ks.fwd_corr};
-    for (const void *f : fns)
-        HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int) std::max(b->shmem, b->shmem_fact)));
+    const Family &f = b->fam;
+    /* (a sixteen-lanes family: the largest of ITS sizes and of the wave-per-instance init / finalize -- the parent of this function
+     * took the two wave-per-instance sweep sizes there; neither reaches 64 KB at nu + nx <= 32, so no call differs) */
+    const size_t most = std::max(std::max(f.lds.fact, f.lds.rhs), std::max(f.lds.fwd, f.lds.whole));
+    if (most <= 64 * 1024) return;
+    const void *fns[] = {(const void *) f.own_ks.back_fact, (const void *) f.own_ks.back_rhs,
+                         (const void *) f.own_ks.fwd_aff, (const void *) f.own_ks.fwd_corr};
+    for (const void *fn : fns)
+        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) most));
 }
 
-/* the kernel set, LDS sizes and name of a batch for its ric_alg (see ocp_qp_gpu_batch::ric_alg) */
+/* the family and name of a batch for its ric_alg (see ocp_qp_gpu_batch::ric_alg) */
 static void ric_configure(ocp_qp_gpu_batch *b)
 {
-    ocp_qp_gpu_batch::Ric1 &r = b->ric1;
     if (b->ric_alg == 1)
     {
-        if (!r.saved) return;
-        if (b->wpi)
-        {
-            b->own_ks = r.own_ks; b->ks = &b->own_ks;
-            b->w16 = r.w16; b->w16_solve = r.w16_solve; b->wpi_mfma = r.wpi_mfma;
-            b->shmem = r.shmem; b->shmem_fwd = r.shmem_fwd; b->shmem_fact = r.shmem_fact;
-            if (b->finalized) wpi_lds_attributes(b);
-        }
-        b->kname = r.kname;
-        r.saved = false;
-        return;
+        if (!b->ric1_saved) return;
+        b->fam = b->ric1_fam;
+        b->ric1_saved = false;
     }
-    if (!r.saved)
+    else
     {
-        r.own_ks = b->own_ks; r.w16 = b->w16; r.w16_solve = b->w16_solve; r.wpi_mfma = b->wpi_mfma;
-        r.shmem = b->shmem; r.shmem_fwd = b->shmem_fwd; r.shmem_fact = b->shmem_fact; r.kname = b->kname;
-        r.saved = true;
+        if (!b->ric1_saved) { b->ric1_fam = b->fam; b->ric1_saved = true; }
+        if (!b->fam.lane()) b->fam = ric0_family(b->fam);
+        b->fam.name = family_name(b->fam, 0);
     }
-    const int wx = b->ks->NX, wu = b->ks->NU, mg = b->ks->NG, ms = b->ks->NS;
-    const size_t con = gqp::wpi_con_doubles(wx + wu, mg, ms);
-    const size_t shmem = (gqp::wpi3_lds_doubles(wx, wu) + con) * sizeof(double);
-    const size_t shmem_fact = (gqp::wpi2_ric0_lds_doubles(wx, wu) + con) * sizeof(double);
-    if (b->wpi)
-    {
-        b->own_ks = wpi_ric0_set(wx, wu, mg, ms);
-        b->ks = &b->own_ks;
-        b->w16 = 0; b->w16_solve = nullptr; b->wpi_mfma = false;
-        b->shmem = shmem; b->shmem_fwd = (gqp::wpi3_lds_doubles(wx, wu, 1) + con) * sizeof(double); b->shmem_fact = shmem_fact;
-        if (b->finalized) wpi_lds_attributes(b);
-    }
-    char nm[160];
-    if (mg || ms) snprintf(nm, sizeof(nm), "wpi-gen(nx=%d,nu=%d,ng=%d,ns=%d,lds=%zuB,ric0)", wx, wu, mg, ms, shmem_fact);
-    else snprintf(nm, sizeof(nm), "wpi-box(nx=%d,nu=%d,lds=%zuB,ric0)", wx, wu, shmem);
-    b->kname = nm;
+    if (!b->fam.lane() && b->finalized) wpi_lds_attributes(b);
 }
 
 void finalize_structure(ocp_qp_gpu_batch *b)
 {
     if (b->finalized) return;
     /* ric_alg 0 set before the structure: the checks below decide for the set ric_alg 1 runs (the sixteen-lanes soft fallback,
-     * the LDS limits); the classical set goes back on afterwards */
-    const bool ric0 = b->ric_alg == 0 && b->ric1.saved;
+     * the LDS limits); the classical family goes back on afterwards */
+    const bool ric0 = b->ric_alg == 0 && b->ric1_saved;
     if (ric0) { b->ric_alg = 1; ric_configure(b); }
-    const int N = b->N, NX = b->ks->NX, NU = b->ks->NU;
+    const int N = b->N, NX = b->fam.ks()->NX, NU = b->fam.ks()->NU;
     const int n = NX + NU, NP = n * (n + 1) / 2;
     b->st.assign(N + 1, GqpStage());
     b->perm.assign(N + 1, std::vector<int>());
@@ -534,9 +860,9 @@ void finalize_structure(ocp_qp_gpu_batch *b)
         if (S.ns > 0) b->has_slack = true;
         S.o_ct = o_ct; S.o_s = o_s; S.o_g = o_g; S.has_dyn = k < N;
         const int nbg = S.nb + S.ng, nct = 2 * nbg + 2 * S.ns;
-        if (nct > 64 * b->AW || nbg > GQP_MAX_ROWS)
+        if (nct > 64 * b->fam.AW || nbg > GQP_MAX_ROWS)
         {
-            fprintf(stderr, "acados_amd: stage %d has %d inequality sides (> %d): unsupported\n", k, nct, 64 * b->AW);
+            fprintf(stderr, "acados_amd: stage %d has %d inequality sides (> %d): unsupported\n", k, nct, 64 * b->fam.AW);
             exit(1); /* not reachable through ocp_qp_gpu_batch_create, which refuses such dims */
         }
         /* sort box rows by variable */
@@ -571,60 +897,14 @@ void finalize_structure(ocp_qp_gpu_batch *b)
         o_ct += nct; o_s += 2 * S.ns; o_g += S.ng;
     }
     b->nct_tot = o_ct; b->ns2_tot = o_s; b->ng_tot = o_g;
-    if (b->w16 && b->w16_soft)
-    {
-        /* the SOFT sixteen-lanes kernels eliminate a slack inside the lane that owns its row: every slack must belong
-         * to exactly one box row that is not an equality-flagged one; anything else runs on the general
-         * wave-per-instance kernels of the same padded dims */
-        bool ok = true;
-        for (int k = 0; k <= N && ok; k++)
-        {
-            const GqpStage &S = b->st[k];
-            std::vector<int> refs(S.ns, 0);
-            for (int r = 0; r < S.nb + (b->w16_ng ? S.ng : 0); r++)
-                if (S.srev[r] >= 0) refs[S.srev[r]]++;
-            for (int q = 0; q < S.ns; q++) ok = ok && refs[q] == 1;
-            if (!b->w16_ng) ok = ok && S.ng == 0;
-            else ok = ok && __builtin_popcountll(S.bmask & ~S.emask) + S.ng <= 16; /* GEN: one inequality row per lane */
-            for (size_t e = 0; e < b->idxe[k].size(); e++) ok = ok && b->idxs_rev[k][b->idxe[k][e]] < 0;
-        }
-        if (!ok)
-        {
-            b->own_ks = b->wpi_ks;
-            b->w16 = 0;
-            b->w16_solve = nullptr;
-            b->w16_soft = false;
-            b->w16_tiles = 0;
-            char nm[160];
-            snprintf(nm, sizeof(nm), "wpi-gen(nx=%d,nu=%d,ng=%d,ns=%d,lds=%zuB)", b->ks->NX, b->ks->NU, b->ks->NG, b->ks->NS, b->shmem_fact);
-            b->kname = nm;
-        }
-    }
-    b->use_box = o_g == 0 && o_s == 0 && !getenv("ACADOS_AMD_GENERAL_KERNELS");
-    b->xbox = 0;
-    for (int k = 0; k <= N; k++)
-        if (((b->st[k].bmask & ~b->st[k].emask) >> NU) != 0) b->xbox = 1;
-    if (b->use_box && !b->wpi)
-    {
-        /* nu + nx <= 6: the pipelined kernels of ipm_kernels_box_small.hpp ("1tpi-pipe"); ACADOS_AMD_KB_SMALL=0 keeps the
-         * phase-ordered ones of ipm_kernels_box.hpp (cross-check) */
-        const char *small = getenv("ACADOS_AMD_KB_SMALL");
-        b->kb_plain = (small && atoi(small) == 0) || NX + NU > 6;
-        char nm[160];
-        snprintf(nm, sizeof(nm), "1tpi-%s<NX=%d,NU=%d,XBOX=%d>", b->kb_plain ? "box" : "pipe", NX, NU, b->xbox);
-        b->kname = nm;
-    }
-    if (b->wpi)
-    {
-        b->use_box = true;
-        wpi_lds_attributes(b); /* more than the default dynamic LDS limit: raised for the four sweep kernels */
-    }
+    family_structure(b->fam, b->st, b->idxs_rev, b->idxe, family_switches());
+    if (!b->fam.lane()) wpi_lds_attributes(b); /* more than the default dynamic LDS limit: raised for the four sweep kernels */
     b->d_st = dalloc<GqpStage>(b, N + 1);
     HIPCHK(hipMemcpy(b->d_st, b->st.data(), sizeof(GqpStage) * (N + 1), hipMemcpyHostToDevice));
 
     GqpDev &D = b->D;
     const size_t Bp = b->Bp;
-    D.B = b->B; D.Bp = b->Bp; D.N = N; D.NX = NX; D.NU = NU; D.NG = b->ks->NG; D.NS = b->ks->NS;
+    D.B = b->B; D.Bp = b->Bp; D.N = N; D.NX = NX; D.NU = NU; D.NG = b->fam.ks()->NG; D.NS = b->fam.ks()->NS;
     D.st = (GqpStagePtr) (uintptr_t) b->d_st;
     const size_t RP = 16; /* spare row elements (clamped dummy row index) */
     D.BAt = garr<double>(b, (size_t) ((N + 1) * n * NX));
@@ -632,8 +912,8 @@ void finalize_structure(ocp_qp_gpu_batch *b)
     D.RSQ = garr<double>(b, (size_t) ((N + 1) * NP));
     D.rq = garr<double>(b, (size_t) ((N + 1) * n));
     D.dvec = garr<double>(b, (size_t) ((o_ct + RP)));
-    D.AW = b->AW;
-    D.amask = garr<uint64_t>(b, (size_t) ((N + 1) * b->AW));
+    D.AW = b->fam.AW;
+    D.amask = garr<uint64_t>(b, (size_t) ((N + 1) * b->fam.AW));
     /* (+ n spare elements: the sixteen-lanes GEN kernels prefetch the stage's rows of [D C] branch-free, a stage WITHOUT general rows
      * reads element 0 of its (empty) block -- for such stages at the end of the horizon that is the element behind the last row:
      * found by the structure fuzz of round 6, seed 9193, a fault only where the array ended on a page boundary) */
@@ -698,8 +978,8 @@ void finalize_structure(ocp_qp_gpu_batch *b)
             m[sp >> 6] &= ~((uint64_t) 1 << (sp & 63));
             m[(nbg + sp) >> 6] &= ~((uint64_t) 1 << ((nbg + sp) & 63));
         }
-        for (int w = 0; w < b->AW; w++)
-            hipLaunchKernelGGL(gqp::k_fill_u64, dim3(grid), dim3(64), 0, b->stream, D.amask, m[w], b->Bp, k * b->AW + w);
+        for (int w = 0; w < b->fam.AW; w++)
+            hipLaunchKernelGGL(gqp::k_fill_u64, dim3(grid), dim3(64), 0, b->stream, D.amask, m[w], b->Bp, k * b->fam.AW + w);
     }
     HIPCHK(hipStreamSynchronize(b->stream));
     b->finalized = true;
@@ -722,7 +1002,7 @@ void ensure_stat(ocp_qp_gpu_batch *b)
 int field_map(ocp_qp_gpu_batch *b, const char *f, int k, std::vector<int> &map, GArr *arr,
               std::vector<int> *map2 = nullptr, GArr *arr2 = nullptr)
 {
-    const int N = b->N, NX = b->ks->NX, NU = b->ks->NU, n = NX + NU, NP = n * (n + 1) / 2;
+    const int N = b->N, NX = b->fam.ks()->NX, NU = b->fam.ks()->NU, n = NX + NU, NP = n * (n + 1) / 2;
     const GqpDev &D = b->D;
     const GqpStage &S = b->st[k];
     const int nx = b->nx[k], nu = b->nu[k], nx1 = k < N ? b->nx[k + 1] : 0;
@@ -962,24 +1242,22 @@ static void copy_level(const GArrT<T> &big, const GArrT<T> &small, const int *d_
 
 extern "C" {
 
-/* force_ks: a compaction sub-batch runs the very kernel set of its parent; force_wpi: a tail / sensitivity sub-batch is
- * pinned to the wave-per-instance family at the parent's padded dims.  Plain arguments: the library keeps no state
- * outside the objects its caller owns (SURVEY 8b "Threading"). */
+/* forced: what a condensed batch or a sub-batch pins of the family choice (ForcedChoice).  Plain arguments: the library keeps no
+ * state outside the objects its caller owns (SURVEY 8b "Threading"). */
 static ocp_qp_gpu_batch *batch_create_shape(int N, const int *nx, const int *nu, const int *nbx, const int *nbu,
-                                            const int *ng, const int *ns, int n_batch, int device, int force_NX, int force_NU,
-                                            const KernelSet *g_force_ks = nullptr, bool g_force_wpi = false);
+                                            const int *ng, const int *ns, int n_batch, int device, const ForcedChoice &forced);
 
 ocp_qp_gpu_batch *ocp_qp_gpu_batch_create(int N, const int *nx, const int *nu, const int *nbx, const int *nbu,
                                           const int *ng, const int *ns, int n_batch, int device)
 try
 {
-    return batch_create_shape(N, nx, nu, nbx, nbu, ng, ns, n_batch, device, 0, 0);
+    return batch_create_shape(N, nx, nu, nbx, nbu, ng, ns, n_batch, device, ForcedChoice());
 }
 catch (const gqp_hip_failure &) { return nullptr; }
 
+/* the object, its family (choose_family), the stream and pinned buffers every batch has */
 static ocp_qp_gpu_batch *batch_create_shape(int N, const int *nx, const int *nu, const int *nbx, const int *nbu,
-                                            const int *ng, const int *ns, int n_batch, int device, int force_NX, int force_NU,
-                                            const KernelSet *g_force_ks, bool g_force_wpi)
+                                            const int *ng, const int *ns, int n_batch, int device, const ForcedChoice &forced)
 {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -990,16 +1268,18 @@ static ocp_qp_gpu_batch *batch_create_shape(int N, const int *nx, const int *nu,
     if (device >= 0) HIPCHK(hipSetDevice(device));
     ocp_qp_gpu_batch *b = new ocp_qp_gpu_batch();
     HIPCHK(hipGetDevice(&b->device));
-    b->force_NX = force_NX; b->force_NU = force_NU;
     b->B = n_batch;
     b->Bp = (n_batch + 63) / 64 * 64;
+    b->w16_slots = n_batch;
     b->N = N;
-    int mx = 0, mu = 0, mg = 0, ms = 0;
+    DimsSummary d;
     for (int k = 0; k <= N; k++)
     {
         b->nx.push_back(nx[k]); b->nu.push_back(nu[k]); b->nbx.push_back(nbx[k]); b->nbu.push_back(nbu[k]);
         b->nb.push_back(nbx[k] + nbu[k]); b->ng.push_back(ng[k]); b->ns.push_back(ns[k]); b->nbxe.push_back(0);
-        mx = std::max(mx, nx[k]); mu = std::max(mu, nu[k]); mg = std::max(mg, ng[k]); ms = std::max(ms, ns[k]);
+        d.mx = std::max(d.mx, nx[k]); d.mu = std::max(d.mu, nu[k]); d.mg = std::max(d.mg, ng[k]); d.ms = std::max(d.ms, ns[k]);
+        d.nct_max = std::max(d.nct_max, 2 * (nbx[k] + nbu[k] + ng[k]) + 2 * ns[k]);
+        d.xbox_dims = d.xbox_dims || (k >= 1 && nbx[k] > 0);
         std::vector<int> ib;
         for (int i = 0; i < nbu[k]; i++) ib.push_back(i);
         for (int i = 0; i < nbx[k]; i++) ib.push_back(nu[k] + i);
@@ -1007,204 +1287,14 @@ static ocp_qp_gpu_batch *batch_create_shape(int N, const int *nx, const int *nu,
         b->idxs_rev.push_back(std::vector<int>(nbx[k] + nbu[k] + ng[k], -1));
         b->idxe.push_back(std::vector<int>());
     }
-    double best = 1e300;
-    auto consider = [&](const KernelSet &ks) {
-        if (ks.NX < mx || ks.NU < mu || ks.NG < mg || ks.NS < ms) return;
-        if (b->force_NX && (ks.NX != b->force_NX || ks.NU != b->force_NU || ks.NG || ks.NS)) return;
-        const double n = ks.NX + ks.NU;
-        const double cost = n * n * n + 10.0 * (ks.NG + ks.NS) * n * n;
-        if (cost < best) { best = cost; b->ks = &ks; }
-    };
-    for (const KernelSet &ks : g_ksets) consider(ks);
+    FamilyChoice choice = choose_family(d, n_batch, forced, family_switches());
+    if (!choice.ok)
     {
-        /* the rolled-loop / scratch-resident instantiations only serve as a cross-check of the wave-per-instance
-         * family (ACADOS_AMD_WPI=0); by default a shape no register-resident instantiation covers goes there */
-        const char *e0 = getenv("ACADOS_AMD_WPI");
-        if (e0 && atoi(e0) == 0)
-            for (int q = 0; q < g_n_ksets_large; q++) consider(g_ksets_large[q]);
-    }
-    if (g_force_ks) b->ks = g_force_ks;
-    /* wave-per-instance family (ipm_kernels_wpi.hpp): box-constrained QPs whose stage block is too large for
-     * the one-instance-per-lane register mapping.  Dimensions are runtime values there: no padding to a
-     * compiled shape.  ACADOS_AMD_WPI=0/1 overrides the size rule (tests). */
-    /* inequality sides per stage: 64 per activity word; the one-instance-per-lane kernels read one word, the
-     * wave-per-instance ones up to two */
-    int nct_max = 0;
-    for (int k = 0; k <= N; k++) nct_max = std::max(nct_max, 2 * (nbx[k] + nbu[k] + ng[k]) + 2 * ns[k]);
-    if (nct_max > 128)
-    {
-        fprintf(stderr, "acados_amd: a stage has %d inequality sides (2(nb+ng)+2ns > 128): unsupported\n", nct_max);
+        fputs(choice.refusal.c_str(), stderr);
         delete b;
         return nullptr;
     }
-    const bool need_wpi = nct_max > 64;
-    if (need_wpi) b->ks = nullptr; /* no one-instance-per-lane kernel may serve it */
-    if (!g_force_ks || g_force_wpi)
-    {
-        int wx = force_NX ? force_NX : mx, wu = force_NU ? force_NU : mu;
-        const bool gen = mg > 0 || ms > 0;
-        const char *env = getenv("ACADOS_AMD_WPI");
-        const char *v1 = getenv("ACADOS_AMD_WPI_V1");
-        const bool ref = v1 && atoi(v1) != 0 && !gen;
-        /* size rule: large stage blocks always; small ones while the batch is too small to fill the chip with 64
-         * instances per wave (measured crossover on the C2 shape between 4,096 and 16,384 instances,
-         * tools/family_crossover.py).  ACADOS_AMD_WPI_BATCH_MAX overrides the batch threshold. */
-        const char *bm = getenv("ACADOS_AMD_WPI_BATCH_MAX");
-        /* sixteen lanes per instance: the smallest compiled shape that covers the dims (per-stage dims live inside
-         * the padded shape); a sub-level created for a hand-over must match its parent's padded dims exactly */
-        const bool soft_dims = mg == 0 && ms > 0; /* slacks on box rows only: the SOFT variants, if the structure allows */
-        const W16Set *w16 = nullptr;
-        {
-            const char *e16 = getenv("ACADOS_AMD_W16"), *e16r = getenv("ACADOS_AMD_W16R");
-            const char *e16g = getenv("ACADOS_AMD_W16G");
-            if (!need_wpi && !ref && !(e16 && atoi(e16) == 0))
-                for (const W16Set &ws : g_w16_sets)
-                {
-                    bool fits = force_NX ? (ws.NX == wx && ws.NU == wu) : (ws.NX >= wx && ws.NU >= wu);
-                    if (!gen) fits = fits && ws.fact && ws.NG == 0;
-                    else if (soft_dims) fits = fits && ws.sfact && ws.NG == 0;                       /* slacks on box rows only */
-                    /* general rows (a small block with a compiled one-instance-per-lane general set -- the golden shared-slack
-                     * structure, nx = 4, nu = 1 -- keeps the dispatch it was measured with: gen_small below) */
-                    else fits = fits && ws.sfact && ws.NG >= mg && !(e16g && atoi(e16g) == 0) && !(b->ks && b->ks->NX + b->ks->NU <= 6);
-                    if (ws.NX + ws.NU > 16 && (e16r && atoi(e16r) == 0)) fits = false;
-                    /* two rows per lane: dims run PADDED inside the compiled shape, so its ~2.3x over the wave-per-instance
-                     * kernels (which take dims at run time) is gone once the padded block has more than twice the work:
-                     * the shape must cover at least 77 % of the compiled nu + nx */
-                    if (ws.NX + ws.NU > 16 && !force_NX && 13 * (wx + wu) < 10 * (ws.NX + ws.NU)) fits = false;
-                    if (fits && (!w16 || ws.NX + ws.NU < w16->NX + w16->NU)) w16 = &ws;
-                }
-        }
-        const bool has_w16 = w16 != nullptr;
-        /* state bounds after stage 0 (the mass-spring class): the one-instance-per-lane kernels of that class run out
-         * of registers, the sixteen-lanes kernels win at every batch size measured (tools/xbox_rate.py) */
-        bool xbox_dims = false;
-        for (int k = 1; k <= N; k++) xbox_dims = xbox_dims || nbx[k] > 0;
-        /* nu + nx <= 6: the pipelined one-instance-per-lane kernels (ipm_kernels_box_small.hpp) take over much earlier
-         * -- measured crossover on nx = 4, nu = 1 between 2,048 and 4,096 instances (N = 100; 4,096 ... 7,281 at N = 20),
-         * with bounds on every state between 7,281 and 16,384; at 65,536 they are 2.7-2.9x (1.4x) ahead
-         * (tools/small_shape_crossover.py) */
-        const bool kb_small = !gen && b->ks && b->ks->NX + b->ks->NU <= 6;
-        /* general rows / shared slacks on a small block with a compiled one-instance-per-lane set (the reference's golden
-         * structure pend_idxs_rev_min_qp0: nx = 4, nu = 1, two general rows sharing one slack): 1,024 instances 3.45 ms
-         * there against 2.65 ms on the wave-per-instance kernels, 8,192: 4.4 against 9.2 ms, 65,536: 8.4 against 74 ms */
-        const bool gen_small = gen && b->ks && b->ks->NX + b->ks->NU <= 6;
-        const int batch_max = bm ? atoi(bm)
-                            : !has_w16 ? (gen_small ? GQP_WPI_GEN_SMALL_MAX : GQP_WPI_BATCH_MAX)
-                            : kb_small ? (xbox_dims ? GQP_W16_SMALL_XBOX_MAX : GQP_W16_SMALL_MAX)
-                            /* general rows / slacks on the sixteen-lanes GEN kernels: the one-instance-per-lane alternative is the
-                             * general set of a (much) larger padded shape with its blocks in scratch -- never */
-                            : (xbox_dims || (gen && !soft_dims && !gen_small) ? INT_MAX : GQP_W16_BATCH_MAX);
-        /* (a shape no compiled one-instance-per-lane set covers runs here whatever the override says) */
-        const bool want = g_force_wpi || need_wpi || !b->ks || (env ? atoi(env) != 0 : (wx + wu >= GQP_WPI_MIN_N || n_batch <= batch_max));
-        if (want && wx + wu <= 64 && wx >= 1 && mg <= 32 && ms <= 32)
-        {
-            if (w16) { wx = w16->NX; wu = w16->NU; }
-            /* factor sweep: register-tile kernel for the tile count of this shape; rhs-only and forward sweeps on
-             * the packed factor; GEN variants carry general constraints and slacks.  ACADOS_AMD_WPI_V1=1 selects
-             * the plain LDS-resident reference kernels of the family (box-constrained QPs only), kept for
-             * cross-checking. */
-            static const kern_redo_t fact_box[8] = {gqp::kw_factor<1, false>, gqp::kw_factor<2, false>, gqp::kw_factor<3, false>,
-                                                    gqp::kw_factor<4, false>, gqp::kw_factor<5, false>, gqp::kw_factor<6, false>,
-                                                    gqp::kw_factor<7, false>, gqp::kw_factor<8, false>};
-            static const kern_redo_t fact_gen[8] = {gqp::kw_factor<1, true>, gqp::kw_factor<2, true>, gqp::kw_factor<3, true>,
-                                                    gqp::kw_factor<4, true>, gqp::kw_factor<5, true>, gqp::kw_factor<6, true>,
-                                                    gqp::kw_factor<7, true>, gqp::kw_factor<8, true>};
-            const int t8 = (wx + wu + 7) / 8 - 1;
-            /* 17 <= n <= 32: blocked Cholesky + the O(n^3) parts on the FP64 matrix pipe (ipm_kernels_wpi_mfma.hpp).
-             * Measured (tools/factor_variants.py, 4,096 instances): C4 class 3.97 vs 4.10 ms per factor launch, box class
-             * nx=24 nu=6 2.40 vs 2.07 ms, condensed C3 shape 0.35 vs 0.33 ms -- the FP64 matrix pipe is slower than the
-             * vector pipe on this chip (tools/mfma_f64_probe), so it serves the class it helps (general rows + slacks) by
-             * default; ACADOS_AMD_WPI_MFMA=1 / 0 forces it on / off for every shape in range */
-            const char *emf = getenv("ACADOS_AMD_WPI_MFMA");
-            const bool mfma = !ref && !w16 && wx + wu > 16 && wx + wu <= 32 && (emf ? atoi(emf) != 0 : gen);
-            kern_redo_t fact_ct = nullptr, rhs_ct = nullptr, faff_ct = nullptr, fcor_ct = nullptr;
-            {
-                /* compile-time dims where they pay: the condensed C3 shape (nx=8 nu=15, box): factor sweep 0.328 -> 0.287 ms
-                 * per 4,096 launch.  Measured and NOT kept: nx=24 nu=3 general (4.09 -> 5.13 ms) and nx=24 nu=6 box (2.07 ->
-                 * 2.15 ms) -- full unrolling costs those shapes more in registers than the folded arithmetic saves
-                 * (tools/factor_variants.py).  ACADOS_AMD_WPI_CT=0 keeps the run-time-shaped instantiations */
-                const char *ect = getenv("ACADOS_AMD_WPI_CT");
-                if (!ref && !w16 && !(ect && atoi(ect) == 0))
-                {
-#define GQP_CT(GENV, X, U, T)                                                                                     \
-    if (gen == GENV && wx == X && wu == U)                                                                        \
-    {                                                                                                             \
-        fact_ct = gqp::kw_factor<T, GENV, X, U>; rhs_ct = gqp::kw_backrhs<GENV, X, U>;                               \
-        faff_ct = gqp::kw_fwd<false, GENV, X, U>; fcor_ct = gqp::kw_fwd<true, GENV, X, U>;                             \
-    }
-                    GQP_CT(false, 8, 15, 3)
-#undef GQP_CT
-                }
-            }
-            static const kern_redo_t fact_mf[2][3] = {{gqp::kw_factor_m<false, 0>, gqp::kw_factor_m<false, 1>, gqp::kw_factor_m<false, 2>},
-                                                      {gqp::kw_factor_m<true, 0>, gqp::kw_factor_m<true, 1>, gqp::kw_factor_m<true, 2>}};
-            const char *epf = getenv("ACADOS_AMD_WPI_MFMA_PF");
-            const int pf = epf ? std::max(0, std::min(2, atoi(epf))) : 0; /* register prefetch did not pay (VGPR pressure) */
-            const kern_redo_t fact = ref ? gqp::kw_backward<true> : mfma ? fact_mf[gen ? 1 : 0][pf] : fact_ct ? fact_ct : gen ? fact_gen[t8] : fact_box[t8];
-            b->wpi_mfma = mfma;
-            kern_redo_t rhs = ref ? gqp::kw_backward<false> : gen ? gqp::kw_backrhs<true> : gqp::kw_backrhs<false>;
-            kern_redo_t faff = ref ? gqp::kw_forward<false> : gen ? gqp::kw_fwd<false, true> : gqp::kw_fwd<false, false>;
-            kern_redo_t fcor = ref ? gqp::kw_forward<true> : gen ? gqp::kw_fwd<true, true> : gqp::kw_fwd<true, false>;
-            if (rhs_ct) { rhs = rhs_ct; faff = faff_ct; fcor = fcor_ct; }
-
-            const kern_opts_t init = gen ? gqp::kw_init<true> : gqp::kw_init<false>;
-            const kern_plain_t fin = gen ? gqp::kw_finalize<true> : gqp::kw_finalize<false>;
-            b->own_ks = KernelSet{wx, wu, mg, ms, init, fact, rhs, faff, fcor, fin,
-                                  {{fact, fact}, {rhs, rhs}, {faff, faff}, {fcor, fcor}}, fin};
-            b->ks = &b->own_ks;
-            b->wpi = 1;
-            b->aos = 1;
-            b->AW = need_wpi ? 2 : 1;
-            /* small box-constrained stage blocks: four instances per wave, register rows + DPP row broadcasts */
-            if (w16)
-            {
-                const W16Set &ws = *w16;
-                b->wpi_ks = b->own_ks; /* what the batch falls back to if the slack structure is not one-slack-per-box-row */
-                const char *et = getenv("ACADOS_AMD_W16T"); /* 0: the factor sweep of the two-rows family on register rows (ky_factor) */
-                const char *etg = getenv("ACADOS_AMD_W16T_GEN"); /* ... of the GEN instantiations alone */
-                const bool tiles = ws.tfact && !(et && atoi(et) == 0) && !(gen && etg && atoi(etg) == 0);
-                const kern_redo_t kf = tiles ? ws.tfact : (gen ? ws.sfact : ws.fact), kr = gen ? ws.srhs : ws.rhs;
-                const kern_redo_t ka = gen ? ws.sfaff : ws.faff, kc = gen ? ws.sfcor : ws.fcor;
-                b->own_ks.back_fact = kf; b->own_ks.back_rhs = kr; b->own_ks.fwd_aff = ka; b->own_ks.fwd_corr = kc;
-                for (int q = 0; q < 2; q++)
-                {
-                    b->own_ks.box.fact[q] = kf; b->own_ks.box.rhs[q] = kr;
-                    b->own_ks.box.fwd_aff[q] = ka; b->own_ks.box.fwd_corr[q] = kc;
-                }
-                b->w16 = 1;
-                b->w16_slots = n_batch;
-                b->w16_soft = gen;
-                b->w16_ng = ws.NG;
-                b->w16_shmem = ws.shmem;
-                b->w16_shmem_fact = tiles ? ws.tshmem : ws.shmem;
-                b->w16_tiles = tiles;
-                if (const char *ea = getenv("ACADOS_AMD_W16_LDS_ALIGN")) /* development: allocation rounded up / padded */
-                {
-                    const size_t a = (size_t) atoi(ea);
-                    if (a > 1) { b->w16_shmem = (b->w16_shmem + a - 1) / a * a; b->w16_shmem_fact = (b->w16_shmem_fact + a - 1) / a * a; }
-                }
-                b->w16_solve = gen ? ws.ssolve : ws.solve;
-            }
-            const size_t con = gqp::wpi_con_doubles(wx + wu, mg, ms);
-            b->shmem = (ref ? gqp::wpi_lds_doubles(wx, wu) : gqp::wpi3_lds_doubles(wx, wu) + con) * sizeof(double);
-            b->shmem_fwd = (ref ? gqp::wpi_lds_doubles(wx, wu) : gqp::wpi3_lds_doubles(wx, wu, 1) + con) * sizeof(double);
-            b->shmem_fact = (ref ? gqp::wpi_lds_doubles(wx, wu) : (mfma ? gqp::wpim_lds_doubles(wx, wu) : gqp::wpi2_lds_doubles(wx, wu)) + con) * sizeof(double);
-        }
-    }
-    if (!b->ks)
-    {
-        fprintf(stderr, "acados_amd: no kernel instantiation covers nx<=%d nu<=%d ng<=%d ns<=%d\n", mx, mu, mg, ms);
-        delete b;
-        return nullptr;
-    }
-    char nm[128];
-    if (b->w16 && b->w16_ng) snprintf(nm, sizeof(nm), "w16r-gen<NX=%d,NU=%d,NG=%d>", b->ks->NX, b->ks->NU, b->w16_ng);
-    else if (b->w16) snprintf(nm, sizeof(nm), b->w16_soft ? "w16-soft<NX=%d,NU=%d>" : b->ks->NX + b->ks->NU > 16 ? "w16r-box<NX=%d,NU=%d>" : "w16-box<NX=%d,NU=%d>", b->ks->NX, b->ks->NU);
-    else if (b->wpi && (b->ks->NG || b->ks->NS))
-        snprintf(nm, sizeof(nm), "wpi-gen(nx=%d,nu=%d,ng=%d,ns=%d,lds=%zuB%s)", b->ks->NX, b->ks->NU, b->ks->NG, b->ks->NS, b->shmem_fact, b->wpi_mfma ? ",mfma" : "");
-    else if (b->wpi) snprintf(nm, sizeof(nm), "wpi-box(nx=%d,nu=%d,lds=%zuB%s)", b->ks->NX, b->ks->NU, b->wpi_mfma ? b->shmem_fact : b->shmem, b->wpi_mfma ? ",mfma" : "");
-    else snprintf(nm, sizeof(nm), "1tpi<NX=%d,NU=%d,NG=%d,NS=%d>", b->ks->NX, b->ks->NU, b->ks->NG, b->ks->NS);
-    b->kname = nm;
+    b->fam = choice.f;
     opts_default(b->O);
     HIPCHK(hipStreamCreate(&b->stream));
     HIPCHK(hipEventCreate(&b->ev0));
@@ -1279,7 +1369,7 @@ try
             if (len == 0) continue;
             if (src_len != len) { src = stage_in(b, data, (size_t) b->B * len, is_device); src_len = len; }
             int *dm = upload_map(b, map);
-            hipLaunchKernelGGL(gqp::k_setmask, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, b->D.amask, k, b->AW);
+            hipLaunchKernelGGL(gqp::k_setmask, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, b->D.amask, k, b->fam.AW);
             continue;
         }
         const int len = field_map(b, f, k, map, &arr, &map2, &arr2);
@@ -1501,7 +1591,7 @@ static void pcond_setup(ocp_qp_gpu_batch *b)
     b->pc = nullptr;
     b->pc_rt = 0;
     for (int q = 0; q < g_n_pcond_sets; q++)
-        if (g_pcond_sets[q].NX == b->ks->NX && g_pcond_sets[q].NU == b->ks->NU && g_pcond_sets[q].BSMAX >= bsmax &&
+        if (g_pcond_sets[q].NX == b->fam.ks()->NX && g_pcond_sets[q].NU == b->fam.ks()->NU && g_pcond_sets[q].BSMAX >= bsmax &&
             (!b->pc || g_pcond_sets[q].BSMAX < b->pc->BSMAX))
             b->pc = &g_pcond_sets[q];
     /* the wave-per-instance condensing kernels take every shape with nx + bs*nu <= 64 at run time; the compiled
@@ -1509,7 +1599,7 @@ static void pcond_setup(ocp_qp_gpu_batch *b)
     {
         const char *e1 = getenv("ACADOS_AMD_PCOND_1TPI");
         const bool want_1tpi = e1 && atoi(e1) != 0 && box_class;
-        if (!(want_1tpi && b->pc) && b->ks->NX + bsmax * b->ks->NU <= 64) b->pc_rt = 1;
+        if (!(want_1tpi && b->pc) && b->fam.ks()->NX + bsmax * b->fam.ks()->NU <= 64) b->pc_rt = 1;
     }
     /* Expansion of a WAVE-TILED parent: element e of eight neighbouring instances shares a 64-byte line, so a kernel that
      * walks one instance per wave moves eight lines for every one it uses -- kw_pexpand is bound by that traffic (13.3 ms
@@ -1517,21 +1607,21 @@ static void pcond_setup(ocp_qp_gpu_batch *b)
      * 1.6 ms.  (Condensing stays with kw_pcond: the per-lane block matrices of k_pcond do not fit the register file.) */
     {
         const char *e2 = getenv("ACADOS_AMD_PCOND_LANE_EXPAND");
-        b->pc_lane_expand = b->pc && b->pc->BSMAX == bsmax && box_class && !b->aos && !(e2 && atoi(e2) == 0);
+        b->pc_lane_expand = b->pc && b->pc->BSMAX == bsmax && box_class && !b->fam.aos && !(e2 && atoi(e2) == 0);
     }
     b->pcz = nullptr;
     {
         const char *e3 = getenv("ACADOS_AMD_PCOND_W16");
         if (box_class && !(e3 && atoi(e3) == 0))
             for (const PcondzSet &z : g_pcondz_sets)
-                if (z.NX == b->ks->NX && z.NU == b->ks->NU && z.BS == bsmax) b->pcz = &z;
+                if (z.NX == b->fam.ks()->NX && z.NU == b->fam.ks()->NU && z.BS == bsmax) b->pcz = &z;
         const char *e4 = getenv("ACADOS_AMD_PCOND_MFMA");
         b->pcz_mfma = !(e4 && atoi(e4) == 0);
     }
     if (!box_class && !b->pc_rt) { decline("the condensed stage (nx + block size * nu > 64) is beyond the condensing kernels"); return; }
     if (!b->pc && !b->pc_rt) { decline("no condensing kernel covers this shape / block size"); return; }
-    const int NU = b->ks->NU, BS = b->pc_rt ? bsmax : b->pc->BSMAX;
-    b->pc_shmem = gqp::pcondw_lds_doubles(b->ks->NX, NU, BS * NU) * sizeof(double);
+    const int NU = b->fam.ks()->NU, BS = b->pc_rt ? bsmax : b->pc->BSMAX;
+    b->pc_shmem = gqp::pcondw_lds_doubles(b->fam.ks()->NX, NU, BS * NU) * sizeof(double);
 
     /* child dims + structure.  Child rows in their original order: [input boxes of the block's stages][state boxes of
      * the block's first stage][general rows: per stage of the block, its state boxes (inner stages) then its general
@@ -1598,7 +1688,7 @@ static void pcond_setup(ocp_qp_gpu_batch *b)
     }
     h_gk[N + 1] = (int) h_grp.size();
     ocp_qp_gpu_batch *c = batch_create_shape(N2, cnx.data(), cnu.data(), cnbx.data(), cnbu.data(), cng.data(), cns.data(),
-                                             b->B, b->device, b->ks->NX, BS * NU);
+                                             b->B, b->device, ForcedChoice{b->fam.ks()->NX, BS * NU});
     if (c && b->stream_priority) set_stream_priority(c, b->stream_priority);
     if (!c) { decline("the condensed shape has no kernel instantiation"); return; }
     if (b->ric_alg != c->ric_alg) ric_switch(c, b->ric_alg); /* condensing never factorises: the child's sweeps carry the choice */
@@ -1643,7 +1733,7 @@ static void pcond_launch(ocp_qp_gpu_batch *b, bool expand)
 {
     ocp_qp_gpu_batch *c = b->child;
     if (!expand) c->held.data_written(true, true); /* the condensing kernels write the child's matrices: it is the root of its own solve */
-    if (!expand && b->pcz && b->pc_rt && b->AW <= 1 && c->AW <= 1)
+    if (!expand && b->pcz && b->pc_rt && b->fam.AW <= 1 && c->fam.AW <= 1)
     {
         const dim3 grid((b->B + 3) / 4, b->pmap.N2 + 1);
         if (b->pcz_mfma)
@@ -1652,7 +1742,7 @@ static void pcond_launch(ocp_qp_gpu_batch *b, bool expand)
         else GQP_LAUNCH_COOP(b->pcz->cond, grid, dim3(64), b->pcz->shmem, b->stream, b->D, c->D, b->pmap);
         return;
     }
-    if ((b->pc_rt || b->AW > 1 || c->AW > 1) && !(expand && b->pc_lane_expand && b->AW <= 1 && c->AW <= 1))
+    if ((b->pc_rt || b->fam.AW > 1 || c->fam.AW > 1) && !(expand && b->pc_lane_expand && b->fam.AW <= 1 && c->fam.AW <= 1))
     {
         /* (the expansion keeps four 64-entry vectors in LDS, not the condensing's block matrices: with the small allocation a CU holds
          *  all the waves its SIMDs take) */
@@ -1733,8 +1823,8 @@ struct IpmKernels
 template <class Kern, class... Args>
 static void launch_level(const ocp_qp_gpu_batch *b, Kern fn, size_t shm, bool sweep, hipStream_t s, const Args &...args)
 {
-    if (sweep && b->w16) GQP_LAUNCH_COOP(fn, dim3((b->w16_slots + 3) / 4), dim3(64), shm, s, args...);
-    else if (b->wpi) GQP_LAUNCH_COOP(fn, dim3(b->B), dim3(64), shm, s, args...);
+    if (sweep && b->fam.w16()) GQP_LAUNCH_COOP(fn, dim3((b->w16_slots + 3) / 4), dim3(64), shm, s, args...);
+    else if (!b->fam.lane()) GQP_LAUNCH_COOP(fn, dim3(b->B), dim3(64), shm, s, args...);
     else hipLaunchKernelGGL(fn, dim3((b->B + 63) / 64), dim3(64), 0, s, args...);
 }
 static void launch_sweep(const ocp_qp_gpu_batch *b, const Sweep &k, hipStream_t s, const GqpDev &D, const GqpOpts &O, int redo)
@@ -1745,28 +1835,27 @@ static void launch_sweep(const ocp_qp_gpu_batch *b, const Sweep &k, hipStream_t 
 template <class Kern, class... Args>
 static void launch_whole(const ocp_qp_gpu_batch *b, Kern fn, hipStream_t s, const Args &...args)
 {
-    launch_level(b, fn, b->shmem, false, s, args...);
+    launch_level(b, fn, b->fam.lds.whole, false, s, args...);
 }
 
 static IpmKernels pick_kernels(const ocp_qp_gpu_batch *b)
 {
-    const KernelSet *ks = b->ks;
-    const int xb = b->xbox;
-    const bool lane_box = b->use_box && !b->wpi;
+    const KernelSet *ks = b->fam.ks();
+    const int xb = b->fam.xbox;
+    const bool lane_box = b->fam.use_box && b->fam.lane();
     /* the family's box sweeps: the serving ones, or the ipm_kernels_box.hpp kernels where the batch asks for them */
-    const BoxSweeps &bx = (lane_box && b->kb_plain && ks->kb.fact[xb]) ? ks->kb : ks->box;
-    const size_t lds_fact = b->w16 ? b->w16_shmem_fact : b->shmem_fact, lds_rhs = b->w16 ? b->w16_shmem : b->shmem;
-    const size_t lds_fwd = b->w16 ? b->w16_shmem : b->shmem_fwd;
+    const BoxSweeps &bx = (lane_box && b->fam.kb_plain && ks->kb.fact[xb]) ? ks->kb : ks->box;
+    const FamilyLds &lds = b->fam.lds;
     IpmKernels k;
-    k.fact = {b->use_box ? bx.fact[xb] : ks->back_fact, lds_fact};
-    k.rhs = {b->use_box ? bx.rhs[xb] : ks->back_rhs, lds_rhs};
-    k.faff = {b->use_box ? bx.fwd_aff[xb] : ks->fwd_aff, lds_fwd};
-    k.fcorr = {b->use_box ? bx.fwd_corr[xb] : ks->fwd_corr, lds_fwd};
+    k.fact = {b->fam.use_box ? bx.fact[xb] : ks->back_fact, lds.fact};
+    k.rhs = {b->fam.use_box ? bx.rhs[xb] : ks->back_rhs, lds.rhs};
+    k.faff = {b->fam.use_box ? bx.fwd_aff[xb] : ks->fwd_aff, lds.fwd};
+    k.fcorr = {b->fam.use_box ? bx.fwd_corr[xb] : ks->fwd_corr, lds.fwd};
     /* held entries: one instance per lane, box rows on the controls only */
     const bool held = lane_box && !xb;
     k.fact_held = {held ? bx.fact_held : nullptr, 0};
     k.rhs_held = {held ? bx.rhs_held : nullptr, 0};
-    k.final_ = b->use_box ? ks->box_finalize : ks->finalize;
+    k.final_ = b->fam.use_box ? ks->box_finalize : ks->finalize;
     return k;
 }
 
@@ -1858,7 +1947,7 @@ void HeldDynamics::begin(ocp_qp_gpu_batch *root, hipStream_t s, bool polish_loop
 {
     b = root;
     polish = polish_loop;
-    enabled = b->hold_dynamics && b->use_box && !b->wpi && !b->w16;
+    enabled = b->hold_dynamics && b->fam.use_box && b->fam.lane();
     pending_ver = 0;
     const size_t bytes = sizeof(int) * (size_t) (b->Bp / 64);
     if (enabled && !polish && kept_at == ver_dyn)
@@ -1980,8 +2069,8 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
      * (65,536 instances, bandwidth-bound: the pass overlaps with other workgroups' sweeps, a launch of its own does not) 48.4 ->
      * 49.4 ms; short horizons (N = 20) lose what one more launch per iteration costs (r05_ext_update_ab2.txt: -2.6 % at nx = 12) -- so:
      * GEN always, box classes up to 16,384 instances from N = 50 on.  ACADOS_AMD_EXT_UPDATE=0 / 1 forces the pass / the launch */
-    const char *eext = getenv("ACADOS_AMD_EXT_UPDATE");
-    const bool ext_update = b->w16 && (eext ? atoi(eext) != 0 : (b->w16_ng > 0 || (b->B <= 16384 && b->N >= 50)));
+    const FamilySwitches sw = family_switches(); /* (read at every solve: tools/ext_update_ab.py changes them between two) */
+    const bool ext_update = b->fam.w16() && (sw.ext_update.set ? sw.ext_update.v != 0 : (b->fam.ng > 0 || (b->B <= 16384 && b->N >= 50)));
     HeldDynamics none; /* a sub-level takes no part -- but for the dense level of an all-held root (compact_into: adopt()) */
     HeldDynamics &H = top ? root->held : b->held.level ? b->held : none;
     HeldDynamics &Hroot = root->held; /* the scalars of the solve */
@@ -1993,12 +2082,11 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
     b->w16_slots = b->B;
     /* sixteen lanes per instance: once a sixth of the slots has converged the sweeps run over a dense list of the live
      * instances (row slot -> instance, GqpDev::perm) -- no data moves, the grid shrinks, every wave carries four live rows */
-    const char *eperm = getenv("ACADOS_AMD_W16_PERM");
-    const bool use_perm = b->w16 && !(eperm && atoi(eperm) == 0);
-    if (top && b->w16 && b->w16_solve && b->B <= root->solve_max && !D.perm)
+    const bool use_perm = b->fam.w16() && !sw.w16_perm.off();
+    if (top && b->fam.w16() && b->fam.solve && b->B <= root->solve_max && !D.perm)
     {
         /* small batch: every 16-lane row runs this loop by itself inside one launch (kx_solve) */
-        prof.timed(1, s, true, [&] { launch_sweep(b, Sweep{b->w16_solve, b->w16_shmem}, s, D, O, 0); });
+        prof.timed(1, s, true, [&] { launch_sweep(b, Sweep{b->fam.solve, b->fam.lds.rhs}, s, D, O, 0); });
         root->launches++;
         root->n_single_launch++;
         HIPCHK(hipMemcpyAsync(b->h_nact, D.n_active, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2045,7 +2133,7 @@ static void run_ipm(ocp_qp_gpu_batch *b, ocp_qp_gpu_batch *root, Prof &prof, hip
         const HeldDynamics *known = &H != &none ? &H : nullptr;
         /* (the tail rule measures the survivors against the ROOT's batch at every level: when the tail takes over, and with it every
          * output bit, does not depend on whether a level was made in between) */
-        if (!b->wpi && root->tail_max > 0 && nact <= root->tail_max && (long) root->tail_div * nact <= root->B)
+        if (b->fam.lane() && root->tail_max > 0 && nact <= root->tail_max && (long) root->tail_div * nact <= root->B)
         {
             /* the last survivors of a one-instance-per-lane level: a wave that still has ONE active lane pays
              * the full per-wave latency of every sweep, so the tail continues one wave per instance */
@@ -2189,14 +2277,18 @@ static void sub_list_reserve(ocp_qp_gpu_batch *b, SubBatch &sb, int n)
     sb.d_list = dalloc<int>(b, n);
 }
 
-/* the sub-batch of `role` for `cap` instances of b: the very kernel set of b (compaction) or the wave-per-instance family at the very
+/* the sub-batch of `role` for `cap` instances of b: the very family of b (compaction) or the wave-per-instance family at the very
  * same padded dims (every other role).  Not being able to make one is a device failure like any other: the entry returns -1 */
 static ocp_qp_gpu_batch *sub_batch_create(ocp_qp_gpu_batch *b, SubRole role, int cap)
 {
     static const char *const names[SUB_ROLES] = {"compaction", "tail", "classical-Riccati", "sensitivity"};
-    const bool wpi = role != SUB_COMPACT;
+    /* the family comes from the role: a compaction level runs its parent's, every other role the wave-per-instance family at the
+     * parent's padded dims (choose_family) */
+    ForcedChoice forced;
+    forced.parent = &b->fam;
+    forced.wpi = role != SUB_COMPACT;
     ocp_qp_gpu_batch *c = batch_create_shape(b->N, b->nx.data(), b->nu.data(), b->nbx.data(), b->nbu.data(), b->ng.data(), b->ns.data(), cap,
-                                             b->device, wpi ? b->ks->NX : 0, wpi ? b->ks->NU : 0, b->ks, wpi);
+                                             b->device, forced);
     if (!c)
     {
         fprintf(stderr, "acados_amd: cannot create the %s sub-batch\n", names[role]);
@@ -2206,11 +2298,7 @@ static ocp_qp_gpu_batch *sub_batch_create(ocp_qp_gpu_batch *b, SubRole role, int
     c->idxb = b->idxb; c->idxs_rev = b->idxs_rev; c->idxe = b->idxe; c->nbxe = b->nbxe;
     switch (role)
     {
-    case SUB_COMPACT: /* the family of the parent goes with its kernel set */
-        c->aos = b->aos; c->wpi = b->wpi; c->shmem = b->shmem; c->shmem_fwd = b->shmem_fwd; c->shmem_fact = b->shmem_fact;
-        c->w16 = b->w16; c->w16_soft = b->w16_soft; c->w16_ng = b->w16_ng; c->w16_shmem = b->w16_shmem;
-        c->w16_shmem_fact = b->w16_shmem_fact; c->w16_tiles = b->w16_tiles;
-        /* fall through */
+    case SUB_COMPACT:
     case SUB_TAIL: /* a level sizes the sub-batches below it by the thresholds it was made under */
         c->compact_min = b->compact_min; c->tail_max = b->tail_max; c->tail_div = b->tail_div;
         break;
@@ -2491,10 +2579,10 @@ try
         if (b->pcond_state == 0) pcond_setup(b);
         if (b->pcond_state == 1) return pcond_solve(b, b->lhs_ready ? 2 : 3);
     }
-    if (b->ric_alg == 0 && !b->wpi) return ric0_solve(b);
+    if (b->ric_alg == 0 && b->fam.lane()) return ric0_solve(b);
     b->time_xcond = 0.0;
     ensure_stat(b);
-    const KernelSet *ks = b->ks;
+    const KernelSet *ks = b->fam.ks();
     GqpDev D = b->D;
     GqpOpts O = effective_opts(b->O, b);
     const dim3 grid((b->B + 63) / 64), block(64);
@@ -2556,7 +2644,7 @@ catch (const gqp_hip_failure &) { return -1; }
  * are restored. */
 static void refactor_at_solution(ocp_qp_gpu_batch *b)
 {
-    if (b->ric_alg == 0 && !b->wpi) { ric0_refactor(b); return; }
+    if (b->ric_alg == 0 && b->fam.lane()) { ric0_refactor(b); return; }
     hipStream_t s = b->stream;
     const dim3 g64((b->B + 63) / 64), blk(64);
     if (!b->d_saved_status) b->d_saved_status = dalloc<int>(b, b->Bp);
@@ -2574,7 +2662,7 @@ static int sens_begin(ocp_qp_gpu_batch *b)
     /* after a partially condensed solve the expanded solution sits in this (full-space) batch: the factorisation at
      * the solution and the seed sweeps run here, the condensed sub-batch is not involved */
     /* a one-instance-per-lane batch hands slices of itself to a wave-per-instance sub-batch in sens_solve */
-    if (b->wpi) refactor_at_solution(b);
+    if (!b->fam.lane()) refactor_at_solution(b);
     const GqpDev &D = b->D;
     const int n = D.NX + D.NU;
     if (!b->sfix.p) b->sfix = garr<double>(b, (size_t) (b->N + 2) * n);
@@ -2704,7 +2792,7 @@ try
     HIPCHK(hipSetDevice(b->device));
     finalize_structure(b);
     if (sens_begin(b)) return -1; /* no seed set: all-zero seeds, zero sensitivities */
-    if (!b->wpi)
+    if (b->fam.lane())
     {
         sens_solve_sliced(b);
         HIPCHK(hipGetLastError());
@@ -2740,7 +2828,7 @@ try
             const size_t mcnt = (size_t) b->B * mlen;
             double *mdst = stage_out(b, data, mcnt, is_device);
             int *dmm = upload_map(b, map);
-            hipLaunchKernelGGL(gqp::k_getmask, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, mdst, b->B, mlen, dmm, b->D.amask, k, b->AW);
+            hipLaunchKernelGGL(gqp::k_getmask, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, mdst, b->B, mlen, dmm, b->D.amask, k, b->fam.AW);
             stage_out_done(b, data, mcnt, is_device);
             return 0;
         }
@@ -2761,7 +2849,7 @@ try
         else if (like)
         {
             len = field_map(b, like, k, map, &arr);
-            if (!strcmp(f, "res_b")) for (int &m : map) m -= b->ks->NX; /* pi lives in slot k+1, res_b in slot k */
+            if (!strcmp(f, "res_b")) for (int &m : map) m -= b->fam.ks()->NX; /* pi lives in slot k+1, res_b in slot k */
             arr = !strcmp(f, "res_g") ? b->R.g : !strcmp(f, "res_b") ? b->R.b : !strcmp(f, "res_d") ? b->R.d : b->R.m;
         }
         else len = -1;
@@ -2865,7 +2953,7 @@ try
 {
     HIPCHK(hipSetDevice(b->device));
     if (b->pcond_state == 1 && b->child) return ocp_qp_gpu_batch_get_stat(b->child, inst, stat, max_rows);
-    if (b->ric_alg == 0 && !b->wpi && b->sub[SUB_RIC0].c) return ocp_qp_gpu_batch_get_stat(b->sub[SUB_RIC0].c, inst, stat, max_rows);
+    if (b->ric_alg == 0 && b->fam.lane() && b->sub[SUB_RIC0].c) return ocp_qp_gpu_batch_get_stat(b->sub[SUB_RIC0].c, inst, stat, max_rows);
     if (!b->D.stat || inst < 0 || inst >= b->stat_inst) return -1;
     const int rows = std::min(max_rows, b->stat_rows);
     std::vector<double> h((size_t) b->stat_rows * GQP_STAT_COLS * b->stat_inst);
@@ -2886,7 +2974,7 @@ try
     if (!strcmp(f, "launches")) return (double) b->launches;
     if (!strcmp(f, "time_xcond")) return b->time_xcond;
     if (!strcmp(f, "compactions")) return (double) b->n_compactions;
-    if (!strcmp(f, "w16_tiles")) return (double) b->w16_tiles;
+    if (!strcmp(f, "w16_tiles")) return (double) b->fam.tiles;
     if (!strcmp(f, "tail_switches")) return (double) b->n_tail_switches;
     if (!strcmp(f, "tiles_invariant")) return (double) b->held.tiles_invariant;
     if (!strcmp(f, "rhs_held_launches")) return (double) b->held.rhs_launches;
@@ -2909,7 +2997,7 @@ try
     if (!strcmp(f, "tol_comp_effective")) { finalize_structure(b); return effective_opts(b->O, b).tol_comp; }
     /* which condensing / expansion kernels serve the batch: 2 sixteen lanes per block, 1 one instance per lane, 0 one wave
      * per instance (meaningful once partial condensing is active) */
-    if (!strcmp(f, "pcond_kernel")) return b->pcond_state != 1 ? -1.0 : (b->pcz && b->pc_rt && b->AW <= 1 && b->child->AW <= 1) ? (b->pcz_mfma ? 3.0 : 2.0) : b->pc_rt ? 0.0 : 1.0;
+    if (!strcmp(f, "pcond_kernel")) return b->pcond_state != 1 ? -1.0 : (b->pcz && b->pc_rt && b->fam.AW <= 1 && b->child->fam.AW <= 1) ? (b->pcz_mfma ? 3.0 : 2.0) : b->pc_rt ? 0.0 : 1.0;
     if (!strcmp(f, "pexpand_kernel")) return b->pcond_state != 1 ? -1.0 : (!b->pc_rt || b->pc_lane_expand) ? 1.0 : 0.0;
     {
         /* accumulated per-kernel-class event times (ms) and launch counts since the last reset */
@@ -3251,7 +3339,7 @@ catch (const gqp_hip_failure &) { if (len) *len = 0; return -1; }
 /* the arrays of a bulk map -> blob (instance-major): as bulk_scatter_launch below */
 static void bulk_gather_launch(ocp_qp_gpu_batch *b, double *dst, int len, const int *d_arr, const int *d_elem, const gqp::GArrTable &T)
 {
-    if (b->aos && !getenv("ACADOS_AMD_SCATTER_PLAIN"))
+    if (b->fam.aos && !getenv("ACADOS_AMD_SCATTER_PLAIN"))
         hipLaunchKernelGGL(gqp::k_bulk_gather_aos, dim3((len + 255) / 256, b->B), dim3(256), 0, b->stream, dst, b->B, len, d_arr, d_elem, T);
     else if (!getenv("ACADOS_AMD_SCATTER_PLAIN"))
         GQP_LAUNCH_COOP(gqp::k_bulk_gather_tile, dim3((b->B + 63) / 64, (len + 63) / 64), dim3(64), 0, b->stream, dst, b->B, len, d_arr, d_elem, T);
@@ -3263,7 +3351,7 @@ static void bulk_gather_launch(ocp_qp_gpu_batch *b, double *dst, int len, const 
  * an LDS tile where they are wave-tiled (ACADOS_AMD_SCATTER_PLAIN=1: one lane per instance, the cross-check) */
 static void bulk_scatter_launch(ocp_qp_gpu_batch *b, const double *src, int len, BulkMap &M)
 {
-    if (b->aos && !getenv("ACADOS_AMD_SCATTER_PLAIN"))
+    if (b->fam.aos && !getenv("ACADOS_AMD_SCATTER_PLAIN"))
         hipLaunchKernelGGL(gqp::k_bulk_scatter_aos, dim3((len + 255) / 256, b->B), dim3(256), 0, b->stream, src, b->B, len, M.d_arr, M.d_elem, M.T);
     else if (!getenv("ACADOS_AMD_SCATTER_PLAIN"))
         GQP_LAUNCH_COOP(gqp::k_bulk_scatter_tile, dim3((b->B + 63) / 64, (len + 63) / 64), dim3(64), 0, b->stream, src, b->B, len, M.d_arr, M.d_elem, M.T);
@@ -3281,7 +3369,7 @@ static void blob_scatter(ocp_qp_gpu_batch *b, BulkMap &M, const double *src)
     bulk_scatter_launch(b, src, M.len, M);
     if (M.nm)
         hipLaunchKernelGGL(gqp::k_bulk_masks, dim3((b->B + 63) / 64, (b->N + 1 + GQP_MASK_SPC - 1) / GQP_MASK_SPC), dim3(64), 0, b->stream, src, b->B, M.len, M.d_moff,
-                           M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->AW, GQP_MASK_SPC);
+                           M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->fam.AW, GQP_MASK_SPC);
 }
 
 /* the caller's blob of a kind: copy (where it is a host pointer) + scatter, timed and waited for */
@@ -3447,7 +3535,7 @@ try
     bulk_gather_launch(b, dst, M.len, M.d_arr_g, M.d_elem_g, M.T);
     if (M.nm)
         hipLaunchKernelGGL(gqp::k_bulk_masks_get, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, dst, b->B, M.len, M.d_moff,
-                           M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->AW);
+                           M.d_mstage, M.d_mbit, M.nm, b->D.amask, b->fam.AW);
     stage_out_done(b, blob, cnt, is_device);
     return 0;
 }
@@ -3534,7 +3622,7 @@ static void grad_build(ocp_qp_gpu_batch *b)
     if (G.built) return;
     const BulkMap &Mi = blob_map(b, BLOB_IN), &Mo = blob_map(b, BLOB_OUT);
     const int len = Mi.len, olen = Mo.len;
-    const int N = b->N, NX = b->ks->NX, NU = b->ks->NU, n = NX + NU, NP = n * (n + 1) / 2;
+    const int N = b->N, NX = b->fam.ks()->NX, NU = b->fam.ks()->NU, n = NX + NU, NP = n * (n + 1) / 2;
     auto ob = [&](const char *f, int k) { int l = 0; const int o = blob_segment(Mo, f, k, &l); return l > 0 ? o : -1; };
     /* output blob: gather map renumbered to the kernel's tables, activity gates, cotangent destinations */
     std::vector<int> oarr(olen, -1), oelem = Mo.elem, ogate(olen, -1), ckind(olen, 0), celem(olen, 0);
@@ -3557,7 +3645,7 @@ static void grad_build(ocp_qp_gpu_batch *b)
             if (f == "lam" || f == "t")
             {
                 const int bit = oelem[o + e] - S.o_ct;
-                ogate[o + e] = (k * b->AW + bit / 64) * 64 + bit % 64;
+                ogate[o + e] = (k * b->fam.AW + bit / 64) * 64 + bit % 64;
                 if (e < 2 * nbg)
                 {
                     const int r = e % nbg; /* original row order: box rows, then general rows */
@@ -3960,7 +4048,7 @@ catch (const gqp_hip_failure &) { return -1; }
 
 size_t ocp_qp_gpu_batch_bytes(const ocp_qp_gpu_batch *b) { return b->bytes; }
 void *ocp_qp_gpu_batch_stream(ocp_qp_gpu_batch *b) { return (void *) b->stream; }
-const char *ocp_qp_gpu_batch_kernel_name(const ocp_qp_gpu_batch *b) { return b->kname.c_str(); }
+const char *ocp_qp_gpu_batch_kernel_name(const ocp_qp_gpu_batch *b) { return b->fam.name.c_str(); }
 
 } /* extern "C" */
 

@@ -167,3 +167,37 @@ def test_every_role_on_one_object(clib):
     _assert_same_solve(want[("solve", 0)], _solve(gb), "ric_alg 0 again")
     gb.opts_set("stream_priority", -1)
     _assert_same_solve(want[("solve", 0)], _solve(gb), "ric_alg 0 after stream_priority -1")
+
+
+@pytest.mark.parametrize("clib", TIERS, indirect=True)
+def test_compaction_level_of_a_two_activity_word_batch(clib):
+    """nx = 30, nu = 3: stage 0 has 2 (30 + 3) = 66 inequality sides, more than one activity word holds, so the batch runs one wave
+    per instance with two words per stage (kernel wpi-box(nx=30,nu=3,lds=19560B)).  Eight instances, N = 3; x0 of instances 1, 3
+    and 6 is scaled by 1e-3, so they finish early and, with compact_min 2, the survivors go on in a compaction level.  That level
+    takes the family of its parent whole (gpu_batch.hip, sub_batch_create), the two activity words included: the solve returns 0
+    failures with at least one compaction, and iterate, iteration counts and statuses are, bit for bit, those of the same batch
+    solved without compaction.
+    Mutation: where the level's family is chosen anew from its dims instead (the parent commit of choose_family), no kernel set
+    serves it -- "cannot create the compaction sub-batch", solve() returns -1 and three instances are left at status -2."""
+    from acados_amd import OcpQpGpuBatch
+    from acados_amd.generators import fill_lqr_batch, lqr_dims, random_lqr_batch
+    n, nx, nu, batch = 3, 30, 3, 8
+    data = random_lqr_batch(N=n, nx=nx, nu=nu, batch=batch, seed=5)
+    data["x0"][[1, 3, 6]] *= 1e-3
+    runs = []
+    for compact_min in (1 << 30, 2):
+        gb = OcpQpGpuBatch(lqr_dims(n, nx, nu), batch, _clib=clib)
+        fill_lqr_batch(gb, data, n)
+        gb.opts_set("tol_stat", 1e-8)
+        gb.opts_set("compact_min", compact_min)
+        gb.opts_set("tail_max", 0)
+        bad = gb.solve()
+        assert gb.kernel_name == "wpi-box(nx=30,nu=3,lds=19560B)", gb.kernel_name
+        assert bad == 0, (compact_min, bad, gb.info("status"))
+        runs.append({"blob": gb.get_bulk(), "iter": gb.info("iter").copy(), "status": gb.info("status").copy(),
+                     "compactions": int(gb.scalar("compactions"))})
+    plain, compacted = runs
+    assert plain["compactions"] == 0 and compacted["compactions"] >= 1
+    assert len(set(plain["iter"].tolist())) >= 2, plain["iter"]      # instances really finish at different iterations
+    for key in ("blob", "iter", "status"):
+        assert np.array_equal(plain[key], compacted[key]), key
