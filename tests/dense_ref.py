@@ -414,3 +414,67 @@ def solve_exact(qp, mu_end=1e-13, max_rounds=20, verbose=False):
     stat = float(np.max(np.abs(H @ wq + g + Aeq.T @ nuq - Ain.T @ lam_full)))
     return wq, off, {"lam_in": lam_full, "nu_eq": nuq, "active": active, "cert": cert, "stationarity": stat, "rounds": rounds,
                      "barrier_iters": it}
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Partial condensing and expansion of ONE block, straight from the formulas, in 80-bit extended precision and with no
+# solver: block variables v = [u_k0; ...; u_{k1-1}; x_k0], T_i the map v -> [u_i; x_i] of stage i and d_i its offset
+# ([u_i; x_i] = T_i v + d_i, from x_{i+1} = [B A]_i [u_i; x_i] + b_i).  What the condensing kernels are compared with
+# entry by entry (tests/test_pcond_stagewise.py).  Box class: no state bounds, general rows or slacks inside a block.
+# Shares no code with oracle/ or the HIP path.
+# ---------------------------------------------------------------------------------------------------------------
+
+def condense_block_ref(qp, k0, k1, dtype=np.longdouble):
+    """stages k0 .. k1 - 1 of qp condensed into one stage: dict of R S Q (Hbar = sum T_i' H_i T_i in blocks, S is nu x nx),
+    r q (gbar = sum T_i'(H_i d_i + g_i)) and, where stage k1 exists, B A b of x_k1 = [B A]_{k1-1} w_{k1-1} + b_{k1-1} in terms
+    of v.  dtype: the precision everything is evaluated in (float64: the plain evaluation the test's tolerance is derived from)"""
+    f = lambda a: np.asarray(a, dtype=dtype)
+    nx0 = int(qp.dims.nx[k0])
+    nus = [int(qp.dims.nu[k]) for k in range(k0, k1)]
+    nuc = sum(nus)
+    nv = nuc + nx0
+    X = np.zeros((nx0, nv), dtype=dtype)          # x_i = X v + c
+    X[:, nuc:] = np.eye(nx0, dtype=dtype)
+    c = np.zeros(nx0, dtype=dtype)
+    Hbar, gbar = np.zeros((nv, nv), dtype=dtype), np.zeros(nv, dtype=dtype)
+    uo = 0
+    for i, k in enumerate(range(k0, k1)):
+        nu, nx = nus[i], int(qp.dims.nx[k])
+        H = np.zeros((nu + nx, nu + nx), dtype=dtype)
+        H[:nu, :nu], H[:nu, nu:], H[nu:, :nu], H[nu:, nu:] = f(qp.R[k]), f(qp.S[k]), f(qp.S[k]).T, f(qp.Q[k])
+        g = np.concatenate([f(qp.r[k]), f(qp.q[k])])
+        T = np.zeros((nu + nx, nv), dtype=dtype)
+        T[:nu, uo:uo + nu] = np.eye(nu, dtype=dtype)
+        T[nu:] = X
+        d = np.concatenate([np.zeros(nu, dtype=dtype), c])
+        Hbar += T.T @ H @ T
+        gbar += T.T @ (H @ d + g)
+        uo += nu
+        if k < qp.N:
+            BA = np.concatenate([f(qp.B[k]), f(qp.A[k])], axis=1)
+            X, c = BA @ T, BA @ d + f(qp.b[k])
+    out = {"R": Hbar[:nuc, :nuc], "S": Hbar[:nuc, nuc:], "Q": Hbar[nuc:, nuc:], "r": gbar[:nuc], "q": gbar[nuc:]}
+    if k1 <= qp.N:
+        out["B"], out["A"], out["b"] = X[:, :nuc], X[:, nuc:], c
+    return out
+
+
+def expand_block_ref(qp, k0, k1, ubar, x0, pi_end=None, dtype=np.longdouble):
+    """the solution of stages k0 .. k1 - 1 from the condensed stage's (ubar, x_k0): u by splitting ubar, the states by forward
+    simulation, and -- pi_end given: the multiplier of the dynamics into stage k1, the condensed stage's pi -- pi of the
+    eliminated dynamics by the adjoint recursion pi_{k-1} = Q_k x_k + S_k' u_k + q_k + A_k' pi_k (no inequality rows on the
+    states inside a block of the box class).  Returns {(field, k): vector}"""
+    f = lambda a: np.asarray(a, dtype=dtype)
+    out, uo = {}, 0
+    x = f(x0)
+    for k in range(k0, k1):
+        nu = int(qp.dims.nu[k])
+        out["u", k], out["x", k] = f(ubar)[uo:uo + nu], x
+        uo += nu
+        if k + 1 < k1:
+            x = f(qp.A[k]) @ x + f(qp.B[k]) @ out["u", k] + f(qp.b[k])
+    if pi_end is not None:
+        out["pi", k1 - 1] = f(pi_end)
+        for k in range(k1 - 1, k0, -1):
+            out["pi", k - 1] = f(qp.Q[k]) @ out["x", k] + f(qp.S[k]).T @ out["u", k] + f(qp.q[k]) + f(qp.A[k]).T @ out["pi", k]
+    return out
