@@ -4049,6 +4049,13 @@ catch (const gqp_hip_failure &) { return -1; }
 size_t ocp_qp_gpu_batch_bytes(const ocp_qp_gpu_batch *b) { return b->bytes; }
 void *ocp_qp_gpu_batch_stream(ocp_qp_gpu_batch *b) { return (void *) b->stream; }
 const char *ocp_qp_gpu_batch_kernel_name(const ocp_qp_gpu_batch *b) { return b->fam.name.c_str(); }
+const char *ocp_qp_gpu_batch_tail_kernel_name(const ocp_qp_gpu_batch *b)
+{
+    /* the tail hangs below the level that handed over (run_ipm): the batch itself, or the compaction level below it */
+    for (; b; b = b->sub[SUB_COMPACT].c)
+        if (b->sub[SUB_TAIL].c) return b->sub[SUB_TAIL].c->fam.name.c_str();
+    return "";
+}
 
 } /* extern "C" */
 

@@ -331,6 +331,11 @@ class OcpQpGpuBatch:
     def kernel_name(self):
         return self._L.ocp_qp_gpu_batch_kernel_name(self._h).decode()
 
+    @property
+    def tail_kernel_name(self):
+        """kernel instantiation of the tail sub-batch the last survivors were handed to ("" where no tail has been made)"""
+        return self._L.ocp_qp_gpu_batch_tail_kernel_name(self._h).decode()
+
     def condensed_kernel_name(self):
         """kernel instantiation serving the condensed batch of the last partially condensed solve (None: not condensed)"""
         h = self._L.ocp_qp_gpu_batch_condensed(self._h)

@@ -262,6 +262,9 @@ size_t ocp_qp_gpu_batch_bytes(const ocp_qp_gpu_batch *b);
 void *ocp_qp_gpu_batch_stream(ocp_qp_gpu_batch *b);
 /* name of the kernel instantiation serving this batch, e.g. "1tpi<NX=8,NU=3,NG=0,NS=0>" */
 const char *ocp_qp_gpu_batch_kernel_name(const ocp_qp_gpu_batch *b);
+/* ... and of the tail sub-batch the last survivors of a one-instance-per-lane batch (or of its compaction level) were handed to
+ * (options tail_max / tail_div); "" where no tail has been made */
+const char *ocp_qp_gpu_batch_tail_kernel_name(const ocp_qp_gpu_batch *b);
 
 #ifdef __cplusplus
 }

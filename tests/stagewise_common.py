@@ -1,5 +1,6 @@
-"""What the stage-wise test files share (test_family_stage_edges.py, test_pcond_stagewise.py): one way to give every stage of any
-batch data of its own, and the table of the solver families with the recipe that pins each of them.
+"""What the stage-wise test files share (test_family_stage_edges.py, test_family_handovers.py, test_pcond_stagewise.py): one way to give
+every stage of any batch data of its own, the table of the solver families with the recipe that pins each of them, the table of the
+hand-overs between them, and the oracle's solve of an instance's read-back QP.
 
 The generators of acados_amd.generators repeat ONE block [B A], one Hessian and one set of bounds over the horizon, so a sweep
 that fetched stage k +- 1's block, mask word, bound vector or descriptor would not be noticed on their data.  stagewise_perturb
@@ -92,10 +93,65 @@ def _chain(**kw):
     return make
 
 
+def structure_cases(qp):
+    """which of the four structure cases a QP holds (as tests/test_data_grad.py::test_random_structures_cover_the_cases finds them)"""
+    seen = set()
+    for k in range(qp.N + 1):
+        if int(qp.dims.ng[k]):
+            seen.add("general")
+        rev = np.asarray(qp.idxs_rev[k]).astype(int)
+        if rev.size and np.any(rev >= 0) and len(set(rev[rev >= 0])) < int(np.sum(rev >= 0)):
+            seen.add("shared")
+        for f in ("lbu_mask", "ubu_mask", "lbx_mask", "ubx_mask", "lg_mask", "ug_mask"):
+            m = np.asarray(getattr(qp, f)[k])
+            if m.size and np.any(m == 0):
+                seen.add("one-sided")
+        if len(qp.idxe[k]):
+            seen.add("x0")
+    return seen
+
+
+def structure_seed(N):
+    """the first seed from 0 whose random_structure_qp of N stages holds a shared slack, a masked side, an equality-flagged x0 and
+    general rows all together (N = 2: seed 9, nx = nu = 3; N = 9: seed 4, nx = 5, nu = 3, slacks at seven stages)"""
+    from random_qp import random_structure_qp
+    if N not in _STRUCT_SEED:
+        _STRUCT_SEED[N] = next(s for s in range(1000) if structure_cases(random_structure_qp(s, N=N)) == {"general", "shared", "one-sided", "x0"})
+    return _STRUCT_SEED[N]
+
+
+_STRUCT_SEED = {}
+
+
+def _struct(N, B, seed):
+    """B copies of ONE random structure; make_batch makes the instances differ through the input blob (instance_noise)"""
+    from random_qp import random_structure_qp
+    return [random_structure_qp(structure_seed(N), N=N)] * B
+
+
+def instance_noise(gb, seed):
+    """q and r of instance i + 0.3 N(0,1), drawn per instance (a stream of its own per (seed, i): batches stay prefixes of one another);
+    bounds and dynamics are untouched, so feasibility is that of the one structure.  Asserted on the blob read back: every instance
+    differs from every other one.  Returns the blob written."""
+    blob = gb.get_bulk_in()
+    for i in range(gb.n_batch):
+        g = np.random.default_rng([seed, i])
+        for k in range(gb.N + 1):
+            for f in LIN:
+                o, n = gb.bulk_offset(0, f, k)
+                if o >= 0 and n > 0:
+                    blob[i, o:o + n] += 0.3 * g.standard_normal(n)
+    gb.set_bulk(blob)
+    back = gb.get_bulk_in()
+    assert np.array_equal(back, blob)
+    assert len({back[i].tobytes() for i in range(gb.n_batch)}) == gb.n_batch
+    return blob
+
+
 # instance i of a generator is the same QP whatever the batch size (counter-based streams), and the perturbation is drawn per
 # (generator, N): the batches of one (row, N) are prefixes of one another, and rows that share a generator solve the same data
 GENERATORS = {"lqr41": _lqr(4, 1), "lqr41x": _lqr(4, 1, xbox=True), "lqr83": _lqr(8, 3), "lqr124": _lqr(12, 4), "lqr815": _lqr(8, 15),
-              "lqr246": _lqr(24, 6), "lqr144": _lqr(14, 4), "chain24": _chain(), "chain8": _chain(nx=8, nu=3, ng=4, nsx=2)}
+              "lqr246": _lqr(24, 6), "lqr144": _lqr(14, 4), "chain24": _chain(), "chain8": _chain(nx=8, nu=3, ng=4, nsx=2), "struct": _struct}
 # generator seed per (generator, N), chosen WITH THE ORACLE ALONE (no kernel took part): the smallest seed from 1 at which the
 # oracle's iteration counts of instances 0, 1, 2 of the perturbed batch take at least two values, so every batch of three or more
 # holds instances that finish at different iterations
@@ -104,14 +160,17 @@ SEEDS["lqr144"].update({2: 2, 9: 2})
 SEEDS["chain24"].update({2: 2})
 
 
-def row_qps(row, N, B):
-    g = FAMILIES[row]["gen_key"]
-    return GENERATORS[g](N, B, SEEDS[g][N])
+def row_seed(row, N, handover=False):
+    r = ROWS[row]
+    return HANDOVER_SEEDS[(r["gen_key"], N, r["unit"])] if handover else SEEDS[r["gen_key"]][N]
 
 
-def perturb_seed(row, N):
-    g = FAMILIES[row]["gen_key"]
-    return 7000 + 100 * SEEDS[g][N] + N
+def row_qps(row, N, B, handover=False):
+    return GENERATORS[ROWS[row]["gen_key"]](N, B, row_seed(row, N, handover))
+
+
+def perturb_seed(row, N, handover=False):
+    return 7000 + 100 * row_seed(row, N, handover) + N
 
 
 W16 = {"ACADOS_AMD_WPI": "1", "ACADOS_AMD_W16": "1"}
@@ -147,6 +206,71 @@ FAMILIES = {
     "wpi-gen": dict(env={"ACADOS_AMD_WPI": "1", "ACADOS_AMD_W16G": "0"}, gen_key="chain24", name=("wpi-gen(",), unit=1, gen=True),
     "ric0": dict(env=W16, opts={"ric_alg": 0}, gen_key="lqr83", name=("wpi-box(", ",ric0"), unit=1),
 }
+# ---- hand-overs (test_family_handovers.py) --------------------------------------------------------------------------------------
+# one-instance-per-lane rows that FAMILIES does not hold: the C2 box kernels, and ONE random structure (tests/random_qp.py) with a
+# shared slack, a masked side, an equality-flagged x0 and general rows, whose instances differ in q and r (instance_noise)
+LANE = {"ACADOS_AMD_WPI": "0"}
+HANDOVER_ROWS = {
+    "1tpi-box<8,3>": dict(env=LANE, gen_key="lqr83", name=("1tpi-box<NX=8,NU=3,XBOX=0",), unit=64),
+    "1tpi-gen/struct": dict(env=LANE, gen_key="struct", name=("1tpi<",), unit=64, gen=True),
+}
+ROWS = dict(FAMILIES, **HANDOVER_ROWS)
+# lane row -> tail family: env steers sub_batch_create (family_switches) beside the row's own switches; tail: what
+# ocp_qp_gpu_batch_tail_kernel_name reports (prefix, then substrings); slow: the tail family costs about a second per instance and
+# stage sweep under host simulation
+HANDOVERS = {
+    "1tpi-box<8,3>/w16-box": dict(row="1tpi-box<8,3>", env={}, tail=("w16-box<NX=8,NU=3>",)),
+    "1tpi-box<8,3>/wpi-box": dict(row="1tpi-box<8,3>", env={"ACADOS_AMD_W16": "0"}, tail=("wpi-box(nx=8,nu=3,",)),
+    "1tpi-pipe/w16-box": dict(row="1tpi-pipe", env={}, tail=("w16-box<NX=4,NU=1>",)),
+    "1tpi-pipe/wpi-box": dict(row="1tpi-pipe", env={"ACADOS_AMD_W16": "0"}, tail=("wpi-box(nx=4,nu=1,",)),
+    "1tpi-pipe/xbox/w16-box": dict(row="1tpi-pipe/xbox", env={}, tail=("w16-box<NX=4,NU=1>",)),
+    "1tpi-pipe/xbox/wpi-box": dict(row="1tpi-pipe/xbox", env={"ACADOS_AMD_W16": "0"}, tail=("wpi-box(nx=4,nu=1,",)),
+    "1tpi-gen/w16r-gen/tiles": dict(row="1tpi-gen", env={}, tail=("w16r-gen<NX=24,NU=3,NG=4>",), slow=True),
+    "1tpi-gen/w16r-gen/rows": dict(row="1tpi-gen", env={"ACADOS_AMD_W16T_GEN": "0"}, tail=("w16r-gen<NX=24,NU=3,NG=4>",),
+                                   slow=True),
+    "1tpi-gen/wpi-gen": dict(row="1tpi-gen", env={"ACADOS_AMD_W16G": "0"}, tail=("wpi-gen(nx=24,nu=3,ng=4,ns=8,",)),
+    "1tpi-gen/struct/wpi-gen": dict(row="1tpi-gen/struct", env={}, tail=("wpi-gen(",)),
+}
+# generator seed per (generator, N, unit of the rows that use it), chosen WITH THE ORACLE ALONE (no kernel took part): the smallest
+# seed from 1 at which the oracle's iteration counts c of the batch satisfy, at both batch sizes B of the unit (HANDOVER_BATCHES):
+# c takes at least three values; some iteration j has 1 <= #{c > j} <= B / 2 (a compaction level is entered with compact_min 2);
+# and for the one-instance-per-lane generators (unit 64, tail cases): max c is attained by exactly ONE instance (the late tail:
+# exactly one survivor) and some j has 1 <= #{c > j} <= B / 4 (the default tail_div); and for the two generators of the combined case
+# (lqr41x, chain24) at the larger B: some j has B / 4 < #{c > j} <= B / 2 (the level is entered before the tail rule holds).  Every test
+# asserts its rule on the counts.
+HANDOVER_BATCHES = {4: (5, 7), 64: (65, 130), 1: (3, 5)}
+HANDOVER_SEEDS = {          # (the values the oracle's counts take at the larger batch size)
+    ("lqr41", 2, 64): 1,      # 3 .. 8
+    ("lqr41", 9, 64): 3,      # 4 .. 10
+    ("lqr41x", 2, 64): 3,     # 3 .. 9
+    ("lqr41x", 9, 64): 5,     # 4 .. 11
+    ("lqr83", 2, 64): 2,      # 4 .. 10
+    ("lqr83", 9, 64): 4,      # 5 .. 11
+    ("chain24", 2, 64): 3,    # 6 .. 12, 14, 15
+    ("chain24", 9, 64): 2,    # 7 .. 15
+    ("struct", 2, 64): 1,     # 5 .. 11     (the seed of the instance noise; the structure: structure_seed)
+    ("struct", 9, 64): 1,     # 10 .. 14
+    ("lqr83", 2, 4): 1,       # 4 .. 8
+    ("lqr83", 9, 4): 2,       # 6 .. 9
+    ("lqr124", 2, 4): 1,      # 5, 6, 8
+    ("lqr124", 9, 4): 1,      # 6 .. 10
+    ("lqr815", 2, 4): 1,      # 5 .. 9
+    ("lqr815", 9, 4): 1,      # 6, 7, 8
+    ("lqr246", 2, 4): 1,      # 5, 6, 7
+    ("lqr246", 9, 4): 1,      # 8, 9, 11
+    ("chain8", 2, 4): 1,      # 5, 7, 8, 9, 11
+    ("chain8", 9, 4): 1,      # 9, 10, 11
+    ("chain24", 2, 4): 1,     # 8, 9, 10, 13
+    ("chain24", 9, 4): 2,     # 9, 11, 12
+    ("lqr83", 2, 1): 1,       # 4, 5, 6
+    ("lqr83", 9, 1): 2,       # 6 .. 9
+    ("lqr815", 2, 1): 11,     # 5 .. 8
+    ("lqr815", 9, 1): 2,      # 6 .. 9
+    ("lqr144", 2, 1): 2,      # 5, 6, 7
+    ("lqr144", 9, 1): 2,      # 6, 8, 9
+    ("chain24", 2, 1): 5,     # 9 .. 13
+    ("chain24", 9, 1): 2,     # 9, 11, 12
+}
 BATCHES = {4: (1, 5, 7), 64: (1, 63, 65, 130), 1: (1, 3)}
 RAGGED = {4: 5, 64: 65, 1: 3}
 # 9: longer than every ring (kbs_pipeline: KBS_DEPTH = KBS_DEPTH_XBOX = 2 records; kx_factor_body: PD = W16Prefetch::FACTOR = 1) and than
@@ -155,15 +279,19 @@ HORIZONS = (1, 2, 3, 9)
 LONG = 9
 
 
-def make_batch(clib, monkeypatch, row, N, B, iter_max=60):
-    """the row's batch of B instances over N stages, made stage-wise, with the options of the family tests: all four tolerances
-    1e-8, no hand-over of the tail (the whole solve stays on the family under test), iter_max 60"""
+def make_batch(clib, monkeypatch, row, N, B, iter_max=60, handover=False):
+    """the row's batch of B instances over N stages, made stage-wise (the structure row: its instances made different), with the
+    options of the family tests: all four tolerances 1e-8, no hand-over of the tail (the whole solve stays on the family under test),
+    iter_max 60; handover: the generator seed of HANDOVER_SEEDS instead of SEEDS"""
     from acados_amd import OcpQpGpuBatch
-    r = FAMILIES[row]
+    r = ROWS[row]
     for k, v in r["env"].items():
         monkeypatch.setenv(k, v)
-    gb = OcpQpGpuBatch.from_qps(row_qps(row, N, B), _clib=clib)
-    stagewise_perturb(gb, perturb_seed(row, N))
+    gb = OcpQpGpuBatch.from_qps(row_qps(row, N, B, handover), _clib=clib)
+    if r["gen_key"] == "struct":
+        instance_noise(gb, perturb_seed(row, N, handover))
+    else:
+        stagewise_perturb(gb, perturb_seed(row, N, handover))
     for f in ("tol_stat", "tol_eq", "tol_ineq", "tol_comp"):
         gb.opts_set(f, 1e-8)
     gb.opts_set("tail_max", 0)
@@ -175,10 +303,36 @@ def make_batch(clib, monkeypatch, row, N, B, iter_max=60):
 
 def check_family(gb, row):
     """after a solve: the row ran on the family it names"""
-    r = FAMILIES[row]
+    r = ROWS[row]
     assert gb.kernel_name.startswith(r["name"][0]) and all(s in gb.kernel_name for s in r["name"][1:]), (row, gb.kernel_name)
     for s, v in r.get("scalars", {}).items():
         assert int(gb.scalar(s)) == v, (row, s, gb.scalar(s))
+
+
+_ORACLE = {}
+
+
+def oracle_solve(gb, blob, i):
+    """(qp, oracle) of the oracle's solve of instance i's own read-back QP; computed once per data (the key is the instance's input
+    blob: rows that share a generator and batches that are prefixes of one another hold the same instance bit for bit)"""
+    from oracle.oracle import OracleQp, default_opts
+    key = (gb.dims.signature(), blob[i].tobytes())
+    if key not in _ORACLE:
+        qp = gb.to_qp(i)
+        o = OracleQp(qp)
+        o.solve(default_opts(tol_stat=1e-8, tol_eq=1e-8, tol_ineq=1e-8, tol_comp=1e-8, iter_max=60))
+        _ORACLE[key] = (qp, o)
+    return _ORACLE[key]
+
+
+def oracle_counts(gb, blob):
+    """the oracle's iteration count of every instance of the batch (every one solved: status 0)"""
+    out = np.zeros(gb.n_batch, dtype=int)
+    for i in range(gb.n_batch):
+        _, o = oracle_solve(gb, blob, i)
+        assert o.status == 0, (i, o.status)
+        out[i] = o.iter
+    return out
 
 
 def compared_lanes(B):

@@ -24,8 +24,8 @@ import numpy as np
 import pytest
 
 from conftest import compare_with_oracle
-from oracle.oracle import OracleQp, default_opts
 from stagewise_common import BATCHES, FAMILIES, HORIZONS, KKT_TOL, LONG, RAGGED, TIERS, check_family, compared_lanes, make_batch
+from stagewise_common import oracle_solve as _oracle
 
 
 @pytest.fixture
@@ -43,21 +43,6 @@ def _grid():
                 for t in tiers:
                     out.append(pytest.param(t.values[0], row, N, B, id=f"{row}-N{N}-B{B}-{t.id}", marks=t.marks))
     return out
-
-
-_ORACLE = {}
-
-
-def _oracle(gb, blob, i):
-    """the oracle's solve of instance i's own read-back QP; computed once per data (the key is the instance's input blob: rows that
-    share a generator and batches that are prefixes of one another hold the same instance bit for bit)"""
-    key = (gb.dims.signature(), blob[i].tobytes())
-    if key not in _ORACLE:
-        qp = gb.to_qp(i)
-        o = OracleQp(qp)
-        o.solve(default_opts(tol_stat=1e-8, tol_eq=1e-8, tol_ineq=1e-8, tol_comp=1e-8, iter_max=60))
-        _ORACLE[key] = (qp, o)
-    return _ORACLE[key]
 
 
 def _fields(row):
