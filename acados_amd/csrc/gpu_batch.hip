@@ -212,7 +212,8 @@ struct BulkMap
     bool built = false;
     int len = 0, nm = 0;
     std::vector<std::string> fields; /* per segment */
-    std::vector<int> seg_stage, seg_off, seg_len;
+    std::vector<int> seg_row, seg_stage, seg_off, seg_len; /* (seg_row: the field's row of k_fields) */
+    bool writes_dyn = false, writes_hess = false; /* a scatter of the kind writes [B A]' / RSQ: no stored held verdict stays */
     std::vector<int> arr, elem;      /* per entry: array of T (-1: none) and element in it; d_arr / d_elem are these (grad_build reads them) */
     int *d_arr = nullptr, *d_elem = nullptr, *d_moff = nullptr, *d_mstage = nullptr, *d_mbit = nullptr;
     int *d_sgn = nullptr, *d_elem2 = nullptr; /* seed blob only: sign of the entry in the residual arrays, slot in sfix */
@@ -997,157 +998,279 @@ void ensure_stat(ocp_qp_gpu_batch *b)
     b->D.stat_inst = b->stat_inst;
 }
 
-/* element map of a numeric field: for every source element e the target element index
- * in `*arr` (units of Bp doubles), or -1.  Returns the field length, -1 if unknown. */
-int field_map(ocp_qp_gpu_batch *b, const char *f, int k, std::vector<int> &map, GArr *arr,
-              std::vector<int> *map2 = nullptr, GArr *arr2 = nullptr)
+/* ---- the fields of the C ABI: one table (k_fields) behind _set, _get, _sens_set, the blob maps and the data gradient ---- */
+
+/* Every per-instance array a device table (gqp::GArrTable) can hold.  A table is a list of these names in the order its kernels
+ * count the slots in; slot_of turns a name into the slot of a table, arr_of into the array of a batch */
+enum Arr
 {
-    const int N = b->N, NX = b->fam.ks()->NX, NU = b->fam.ks()->NU, n = NX + NU, NP = n * (n + 1) / 2;
-    const GqpDev &D = b->D;
-    const GqpStage &S = b->st[k];
-    const int nx = b->nx[k], nu = b->nu[k], nx1 = k < N ? b->nx[k + 1] : 0;
-    const int nbu = b->nbu[k], nbx = b->nbx[k], ng = S.ng, ns = S.ns, nbg = S.nb + S.ng;
-    map.clear();
-    auto dyn = [&]() { return k < N; };
-    if (!strcmp(f, "A"))
+    ARR_NONE = -1,
+    ARR_BAt, ARR_bvec, ARR_RSQ, ARR_rq, ARR_dvec, ARR_DCt, ARR_Zz, ARR_ux, ARR_sv, ARR_pi, ARR_lam, ARR_t, /* data and iterate */
+    ARR_dux, ARR_dsv, ARR_dpi, ARR_dlam, ARR_dt, /* directions of a seed pass, in the order of ux .. t (direction_of) */
+    ARR_rg, ARR_rgs, ARR_rb, ARR_rd,             /* residuals: where the seeds go */
+    ARR_Lf, ARR_lf,                              /* factor of the last factorisation */
+    ARR_DEV_END,                                 /* ... so far members of GqpDev; the batch's own: */
+    ARR_sfix = ARR_DEV_END, ARR_cot, ARR_res_g, ARR_res_gs, ARR_res_b, ARR_res_d, ARR_res_m
+};
+typedef GArr GqpDev::*GqpArrMember;
+
+GArr arr_of(const ocp_qp_gpu_batch *b, Arr a)
+{
+    static const GqpArrMember dev[ARR_DEV_END] = {&GqpDev::BAt, &GqpDev::bvec, &GqpDev::RSQ, &GqpDev::rq, &GqpDev::dvec, &GqpDev::DCt, &GqpDev::Zz,
+                                                  &GqpDev::ux, &GqpDev::sv, &GqpDev::pi, &GqpDev::lam, &GqpDev::t, &GqpDev::dux, &GqpDev::dsv,
+                                                  &GqpDev::dpi, &GqpDev::dlam, &GqpDev::dt, &GqpDev::rg, &GqpDev::rgs, &GqpDev::rb, &GqpDev::rd,
+                                                  &GqpDev::Lf, &GqpDev::lf};
+    if (a >= 0 && a < ARR_DEV_END) return b->D.*dev[a];
+    switch (a)
     {
-        if (!dyn()) return -1;
-        *arr = D.BAt;
-        for (int c = 0; c < nx; c++) for (int r = 0; r < nx1; r++) map.push_back((k * n + NU + c) * NX + r);
+    case ARR_sfix: return b->sfix;
+    case ARR_cot: return b->grad.cot;
+    case ARR_res_g: return b->R.g;
+    case ARR_res_gs: return b->R.gs;
+    case ARR_res_b: return b->R.b;
+    case ARR_res_d: return b->R.d;
+    case ARR_res_m: return b->R.m;
+    default: return GArr{nullptr, 0, 0};
     }
-    else if (!strcmp(f, "B"))
-    {
-        if (!dyn()) return -1;
-        *arr = D.BAt;
-        for (int c = 0; c < nu; c++) for (int r = 0; r < nx1; r++) map.push_back((k * n + c) * NX + r);
-    }
-    else if (!strcmp(f, "b"))
-    {
-        if (!dyn()) return -1;
-        *arr = D.bvec;
-        for (int r = 0; r < nx1; r++) map.push_back(k * NX + r);
-    }
-    else if (!strcmp(f, "Q"))
-    {
-        *arr = D.RSQ;
-        for (int c = 0; c < nx; c++) for (int r = 0; r < nx; r++) map.push_back(r >= c ? k * NP + PK(NU + r, NU + c) : -1);
-    }
-    else if (!strcmp(f, "R"))
-    {
-        *arr = D.RSQ;
-        for (int c = 0; c < nu; c++) for (int r = 0; r < nu; r++) map.push_back(r >= c ? k * NP + PK(r, c) : -1);
-    }
-    else if (!strcmp(f, "S"))
-    {
-        *arr = D.RSQ; /* S is nu x nx: u'Sx */
-        for (int jx = 0; jx < nx; jx++) for (int iu = 0; iu < nu; iu++) map.push_back(k * NP + PK(NU + jx, iu));
-    }
-    else if (!strcmp(f, "q")) { *arr = D.rq; for (int r = 0; r < nx; r++) map.push_back(k * n + NU + r); }
-    else if (!strcmp(f, "r")) { *arr = D.rq; for (int r = 0; r < nu; r++) map.push_back(k * n + r); }
-    else if (!strcmp(f, "lbu") || !strcmp(f, "ubu") || !strcmp(f, "lbx") || !strcmp(f, "ubx"))
-    {
-        const bool up = f[0] == 'u', isx = f[2] == 'x';
-        *arr = D.dvec;
-        const int cnt = isx ? nbx : nbu, off = isx ? nbu : 0;
-        for (int e = 0; e < cnt; e++) map.push_back(S.o_ct + (up ? nbg : 0) + b->perm[k][off + e]);
-        if (!up && isx && map2)
-        {
-            /* equality-flagged x bounds: the bound value is the value of the variable */
-            *arr2 = D.ux;
-            map2->assign(cnt, -1);
-            for (size_t q = 0; q < b->idxe[k].size(); q++)
-            {
-                const int ob = b->idxe[k][q];
-                if (ob >= off && ob < off + cnt) (*map2)[ob - off] = k * n + padded_var(b, k, b->idxb[k][ob]);
-            }
-        }
-    }
-    else if (!strcmp(f, "lg") || !strcmp(f, "ug"))
-    {
-        *arr = D.dvec;
-        for (int g = 0; g < ng; g++) map.push_back(S.o_ct + (f[0] == 'u' ? nbg : 0) + S.nb + g);
-    }
-    else if (!strcmp(f, "C"))
-    {
-        *arr = D.DCt;
-        for (int c = 0; c < nx; c++) for (int g = 0; g < ng; g++) map.push_back((S.o_g + g) * n + NU + c);
-    }
-    else if (!strcmp(f, "D"))
-    {
-        *arr = D.DCt;
-        for (int c = 0; c < nu; c++) for (int g = 0; g < ng; g++) map.push_back((S.o_g + g) * n + c);
-    }
-    else if (!strcmp(f, "Zl")) { *arr = D.Zz; for (int j = 0; j < ns; j++) map.push_back((S.o_s + j) * 2); }
-    else if (!strcmp(f, "zl")) { *arr = D.Zz; for (int j = 0; j < ns; j++) map.push_back((S.o_s + j) * 2 + 1); }
-    else if (!strcmp(f, "Zu")) { *arr = D.Zz; for (int j = 0; j < ns; j++) map.push_back((S.o_s + ns + j) * 2); }
-    else if (!strcmp(f, "zu")) { *arr = D.Zz; for (int j = 0; j < ns; j++) map.push_back((S.o_s + ns + j) * 2 + 1); }
-    else if (!strcmp(f, "lls")) { *arr = D.dvec; for (int j = 0; j < ns; j++) map.push_back(S.o_ct + 2 * nbg + j); }
-    else if (!strcmp(f, "lus")) { *arr = D.dvec; for (int j = 0; j < ns; j++) map.push_back(S.o_ct + 2 * nbg + ns + j); }
-    /* iterate */
-    else if (!strcmp(f, "x")) { *arr = D.ux; for (int r = 0; r < nx; r++) map.push_back(k * n + NU + r); }
-    else if (!strcmp(f, "u")) { *arr = D.ux; for (int r = 0; r < nu; r++) map.push_back(k * n + r); }
-    else if (!strcmp(f, "sl")) { *arr = D.sv; for (int j = 0; j < ns; j++) map.push_back(S.o_s + j); }
-    else if (!strcmp(f, "su")) { *arr = D.sv; for (int j = 0; j < ns; j++) map.push_back(S.o_s + ns + j); }
-    else if (!strcmp(f, "pi"))
-    {
-        if (!dyn()) return -1;
-        *arr = D.pi; /* acados pi[k] = multiplier of the dynamics producing x_{k+1}: slot k+1 */
-        for (int r = 0; r < nx1; r++) map.push_back((k + 1) * NX + r);
-    }
-    else if (!strcmp(f, "ric_L"))
-    {
-        /* Cholesky factor of the stage matrix of the last factorisation, variables [u;x] of this
-         * stage (padding removed), nv x nv column-major, lower triangle (upper = 0).
-         * ric_alg 0 (classical layout, get_int "ric_alg"), stages k >= 1: columns 0..nu-1 as above ([Lu; Lxu], the factor of
-         * R~ + B'PB and its coupling rows), the trailing x-block is the lower triangle of P_k itself; ric_l = [lu; p_k].
-         * Stage 0 is the full factor in both layouts. */
-        *arr = D.Lf;
-        const int nv = nu + nx;
-        for (int c = 0; c < nv; c++)
-            for (int r = 0; r < nv; r++)
-                map.push_back(r >= c ? k * NP + PK(padded_var(b, k, r), padded_var(b, k, c)) : -1);
-    }
-    else if (!strcmp(f, "ric_l"))
-    {
-        *arr = D.lf;
-        for (int r = 0; r < nu + nx; r++) map.push_back(k * n + padded_var(b, k, r));
-    }
-    else if (!strcmp(f, "lam") || !strcmp(f, "t"))
-    {
-        *arr = f[0] == 'l' ? D.lam : D.t;
-        for (int side = 0; side < 2; side++)
-        {
-            for (int r = 0; r < S.nb; r++) map.push_back(S.o_ct + side * nbg + b->perm[k][r]);
-            for (int g = 0; g < ng; g++) map.push_back(S.o_ct + side * nbg + S.nb + g);
-        }
-        for (int j = 0; j < 2 * ns; j++) map.push_back(S.o_ct + 2 * nbg + j);
-    }
-    else
-        return -1;
-    return (int) map.size();
 }
 
-/* bit positions of a mask field */
-int mask_bits(ocp_qp_gpu_batch *b, const char *f, int k, std::vector<int> &bits)
+/* the direction array behind sens_<field>: an iterate array has one */
+Arr direction_of(Arr a) { return a >= ARR_ux && a <= ARR_t ? Arr(ARR_dux + (a - ARR_ux)) : ARR_NONE; }
+
+/* the three device tables.  State: the blob scatter / gather kernels (every kind but the seeds).  Seeds: k_bulk_scatter_seed (slot 4
+ * is where it writes the derivative of a fixed variable).  Gradient: k_data_grad (a solution array and its direction are 5 apart) */
+const Arr k_state_arrays[] = {ARR_BAt, ARR_bvec, ARR_RSQ, ARR_rq, ARR_dvec, ARR_DCt, ARR_Zz, ARR_ux, ARR_sv, ARR_pi, ARR_lam, ARR_t};
+const Arr k_seed_arrays[] = {ARR_rg, ARR_rgs, ARR_rb, ARR_rd, ARR_sfix};
+const Arr k_grad_arrays[] = {ARR_ux, ARR_sv, ARR_pi, ARR_lam, ARR_t, ARR_dux, ARR_dsv, ARR_dpi, ARR_dlam, ARR_dt, ARR_RSQ, ARR_BAt, ARR_DCt, ARR_cot};
+
+template <size_t n>
+int slot_of(const Arr (&table)[n], Arr a)
 {
-    const GqpStage &S = b->st[k];
-    const int nbu = b->nbu[k], nbx = b->nbx[k], nbg = S.nb + S.ng, ns = S.ns;
-    bits.clear();
-    std::vector<char> is_eq(S.nb, 0);
-    for (size_t e = 0; e < b->idxe[k].size(); e++) is_eq[b->idxe[k][e]] = 1;
-    auto box = [&](int off, int cnt, int side) {
-        for (int e = 0; e < cnt; e++) bits.push_back(is_eq[off + e] ? -1 : side * nbg + b->perm[k][off + e]);
-    };
-    if (!strcmp(f, "lbu_mask")) box(0, nbu, 0);
-    else if (!strcmp(f, "ubu_mask")) box(0, nbu, 1);
-    else if (!strcmp(f, "lbx_mask")) box(nbu, nbx, 0);
-    else if (!strcmp(f, "ubx_mask")) box(nbu, nbx, 1);
-    else if (!strcmp(f, "lg_mask")) for (int g = 0; g < S.ng; g++) bits.push_back(S.nb + g);
-    else if (!strcmp(f, "ug_mask")) for (int g = 0; g < S.ng; g++) bits.push_back(nbg + S.nb + g);
-    else if (!strcmp(f, "lls_mask")) for (int j = 0; j < ns; j++) bits.push_back(2 * nbg + j);
-    else if (!strcmp(f, "lus_mask")) for (int j = 0; j < ns; j++) bits.push_back(2 * nbg + ns + j);
-    else return -1;
-    return (int) bits.size();
+    for (size_t q = 0; q < n; q++) if (table[q] == a) return (int) q;
+    return -1;
+}
+
+template <size_t n>
+void table_fill(const ocp_qp_gpu_batch *b, gqp::GArrTable &T, const Arr (&table)[n])
+{
+    for (size_t q = 0; q < 16; q++) T.a[q] = q < n ? arr_of(b, table[q]) : GArr{nullptr, 0, 0};
+}
+
+/* One row per field name.  `arr` and `rule` say where element e of the field lives (rule: the element of arr per entry, in units
+ * of Bp doubles, -1 for none; a mask's bit in the activity words of its stage); cls / up / p are the rule's parameters: the
+ * variables (u, x) or the rows (u box, x box, general, slack) the field ranges over, the upper side, a position.  `seed` / `sign`:
+ * the residual array seed_<name> goes to and the sign it is stored with there (lower bounds negated; the slack lower bounds
+ * lls, lus are both lower bounds).  `grad`: what the data gradient of an entry is (grad_build), ga / gb the output-blob fields of
+ * its factors, gc its coefficient */
+enum Cls { C_NONE, C_U, C_X, C_BU, C_BX, C_G, C_S };
+enum
+{
+    F_DYN = 1,   /* lives at the stages 0 .. N-1 only */
+    F_SYM = 2,   /* the packed lower triangle holds the matrix: a READ mirrors it */
+    F_MASK = 4,  /* activity bits, not doubles */
+    F_VALUE = 8, /* an equality-flagged row's entry is also the value of its variable (second map, into ux / sfix) */
+    F_RES = 16   /* residual of the last _res_compute: read only */
+};
+enum GradKind { G_NONE, G_VEC, G_PROD, G_DIAG, G_GEN, G_CT };
+struct FieldCtx;
+struct FieldRow
+{
+    const char *name;
+    Arr arr;
+    void (*rule)(const FieldCtx &, const FieldRow &, std::vector<int> &);
+    Cls cls = C_NONE;
+    int up = 0, p = 0;
+    unsigned flags = 0;
+    Arr seed = ARR_NONE;
+    int sign = 1;
+    GradKind grad = G_NONE;
+    const char *ga = nullptr, *gb = nullptr;
+    double gc = 1.0;
+};
+
+/* what the rules see of one stage */
+struct FieldCtx
+{
+    const ocp_qp_gpu_batch *b;
+    const int k;
+    const GqpStage &S;
+    const int NX, NU, n, NP, nx, nu, nx1, nbu, nbx, ng, ns, nbg;
+    FieldCtx(const ocp_qp_gpu_batch *b_, int k_)
+        : b(b_), k(k_), S(b_->st[k_]), NX(b_->fam.ks()->NX), NU(b_->fam.ks()->NU), n(NX + NU), NP(n * (n + 1) / 2), nx(b_->nx[k_]), nu(b_->nu[k_]),
+          nx1(k_ < b_->N ? b_->nx[k_ + 1] : 0), nbu(b_->nbu[k_]), nbx(b_->nbx[k_]), ng(S.ng), ns(S.ns), nbg(S.nb + S.ng) {}
+    /* the variables of a class: how many, and where they start in the padded [u(NU); x(NX)] */
+    int nvar(Cls c) const { return c == C_X ? nx : nu; }
+    int voff(Cls c) const { return c == C_X ? NU : 0; }
+    int pv(int iv) const { return padded_var(b, k, iv); }
+    /* inequality sides, counted as lam / t list them: lower then upper side of the box rows (the caller's order) and the general
+     * rows, then the lower bounds of sl and of su.  ct_row: the row of entry e of a bound field among box + general rows; ct_pos:
+     * its side; ct_dev: where a side lives in dvec / lam / t / the activity bits (box rows sorted there) */
+    int ct_count(Cls c) const { return c == C_BU ? nbu : c == C_BX ? nbx : c == C_G ? ng : ns; }
+    int ct_row(const FieldRow &r, int e) const { return (r.cls == C_BU ? 0 : r.cls == C_BX ? nbu : S.nb) + e; }
+    int ct_pos(const FieldRow &r, int e) const { return r.cls == C_S ? 2 * nbg + r.up * ns + e : r.up * nbg + ct_row(r, e); }
+    int ct_dev(int pos) const
+    {
+        if (pos >= 2 * nbg) return pos;
+        const int row = pos % nbg;
+        return pos - row + (row < S.nb ? b->perm[k][row] : row);
+    }
+    bool eq(int row) const { return row < S.nb && std::find(b->idxe[k].begin(), b->idxe[k].end(), row) != b->idxe[k].end(); }
+    bool ct_eq(const FieldRow &r, int e) const { return r.cls != C_S && eq(ct_row(r, e)); }
+};
+
+void rule_dyn_mat(const FieldCtx &c, const FieldRow &r, std::vector<int> &m) /* A, B: columns of [B A]' */
+{
+    for (int j = 0; j < c.nvar(r.cls); j++) for (int i = 0; i < c.nx1; i++) m.push_back((c.k * c.n + c.voff(r.cls) + j) * c.NX + i);
+}
+void rule_dyn_vec(const FieldCtx &c, const FieldRow &r, std::vector<int> &m) /* b; acados pi[k] = multiplier of the dynamics producing x_{k+1}: slot k+1 */
+{
+    for (int i = 0; i < c.nx1; i++) m.push_back((c.k + r.p) * c.NX + i);
+}
+void rule_hess(const FieldCtx &c, const FieldRow &r, std::vector<int> &m) /* Q, R */
+{
+    const int d = c.nvar(r.cls), o = c.voff(r.cls);
+    for (int j = 0; j < d; j++) for (int i = 0; i < d; i++) m.push_back(i >= j ? c.k * c.NP + PK(o + i, o + j) : -1);
+}
+void rule_cross(const FieldCtx &c, const FieldRow &, std::vector<int> &m) /* S is nu x nx: u'Sx */
+{
+    for (int jx = 0; jx < c.nx; jx++) for (int iu = 0; iu < c.nu; iu++) m.push_back(c.k * c.NP + PK(c.NU + jx, iu));
+}
+void rule_var(const FieldCtx &c, const FieldRow &r, std::vector<int> &m) /* q r x u */
+{
+    for (int i = 0; i < c.nvar(r.cls); i++) m.push_back(c.k * c.n + c.voff(r.cls) + i);
+}
+void rule_gen_mat(const FieldCtx &c, const FieldRow &r, std::vector<int> &m) /* C, D: rows of [D C] */
+{
+    for (int j = 0; j < c.nvar(r.cls); j++) for (int g = 0; g < c.ng; g++) m.push_back((c.S.o_g + g) * c.n + c.voff(r.cls) + j);
+}
+void rule_penalty(const FieldCtx &c, const FieldRow &r, std::vector<int> &m) /* (Z, z) pairs */
+{
+    for (int j = 0; j < c.ns; j++) m.push_back((c.S.o_s + r.up * c.ns + j) * 2 + r.p);
+}
+void rule_slack(const FieldCtx &c, const FieldRow &r, std::vector<int> &m) /* sl su, and the seeds of zl zu in rgs */
+{
+    for (int j = 0; j < c.ns; j++) m.push_back(c.S.o_s + r.up * c.ns + j);
+}
+void rule_slack_both(const FieldCtx &c, const FieldRow &, std::vector<int> &m) /* [sl; su] */
+{
+    for (int j = 0; j < 2 * c.ns; j++) m.push_back(c.S.o_s + j);
+}
+void rule_ct(const FieldCtx &c, const FieldRow &r, std::vector<int> &m) /* a bound field, or its mask (equality-flagged rows: no bit) */
+{
+    for (int e = 0; e < c.ct_count(r.cls); e++)
+    {
+        const int d = c.ct_dev(c.ct_pos(r, e));
+        m.push_back(r.flags & F_MASK ? (c.ct_eq(r, e) ? -1 : d) : c.S.o_ct + d);
+    }
+}
+void rule_ct_all(const FieldCtx &c, const FieldRow &, std::vector<int> &m) /* lam, t */
+{
+    for (int pos = 0; pos < 2 * c.nbg + 2 * c.ns; pos++) m.push_back(c.S.o_ct + c.ct_dev(pos));
+}
+/* Cholesky factor of the stage matrix of the last factorisation, variables [u;x] of this stage (padding removed), nv x nv
+ * column-major, lower triangle (upper = 0).
+ * ric_alg 0 (classical layout, get_int "ric_alg"), stages k >= 1: columns 0..nu-1 as above ([Lu; Lxu], the factor of
+ * R~ + B'PB and its coupling rows), the trailing x-block is the lower triangle of P_k itself; ric_l = [lu; p_k].
+ * Stage 0 is the full factor in both layouts. */
+void rule_fact_mat(const FieldCtx &c, const FieldRow &, std::vector<int> &m)
+{
+    const int nv = c.nu + c.nx;
+    for (int j = 0; j < nv; j++) for (int i = 0; i < nv; i++) m.push_back(i >= j ? c.k * c.NP + PK(c.pv(i), c.pv(j)) : -1);
+}
+void rule_fact_vec(const FieldCtx &c, const FieldRow &, std::vector<int> &m) /* [u; x] of the stage */
+{
+    for (int i = 0; i < c.nu + c.nx; i++) m.push_back(c.k * c.n + c.pv(i));
+}
+
+/* a bound field and its mask */
+#define GQP_CT_ROWS(name, cls, up, sign, flags) \
+    {name, ARR_dvec, rule_ct, cls, up, 0, flags, ARR_rd, sign, G_CT}, {name "_mask", ARR_NONE, rule_ct, cls, up, 0, F_MASK}
+const FieldRow k_fields[] = {
+    /* name, array, rule, class, upper, p, flags, seed array, seed sign, gradient kind, its factors, its coefficient */
+    {"A", ARR_BAt, rule_dyn_mat, C_X, 0, 0, F_DYN, ARR_NONE, 1, G_PROD, "pi", "x"},
+    {"B", ARR_BAt, rule_dyn_mat, C_U, 0, 0, F_DYN, ARR_NONE, 1, G_PROD, "pi", "u"},
+    {"b", ARR_bvec, rule_dyn_vec, C_NONE, 0, 0, F_DYN, ARR_rb, 1, G_VEC, "pi"},
+    {"Q", ARR_RSQ, rule_hess, C_X, 0, 0, F_SYM, ARR_NONE, 1, G_PROD, "x", "x", 0.5},
+    {"R", ARR_RSQ, rule_hess, C_U, 0, 0, F_SYM, ARR_NONE, 1, G_PROD, "u", "u", 0.5},
+    {"S", ARR_RSQ, rule_cross, C_NONE, 0, 0, 0, ARR_NONE, 1, G_PROD, "u", "x"},
+    {"q", ARR_rq, rule_var, C_X, 0, 0, 0, ARR_rg, 1, G_VEC, "x"},
+    {"r", ARR_rq, rule_var, C_U, 0, 0, 0, ARR_rg, 1, G_VEC, "u"},
+    GQP_CT_ROWS("lbu", C_BU, 0, -1, 0),
+    GQP_CT_ROWS("ubu", C_BU, 1, 1, 0),
+    GQP_CT_ROWS("lbx", C_BX, 0, -1, F_VALUE),
+    GQP_CT_ROWS("ubx", C_BX, 1, 1, 0),
+    GQP_CT_ROWS("lg", C_G, 0, -1, 0),
+    GQP_CT_ROWS("ug", C_G, 1, 1, 0),
+    GQP_CT_ROWS("lls", C_S, 0, -1, 0),
+    GQP_CT_ROWS("lus", C_S, 1, -1, 0), /* su >= lus is a LOWER bound of the slack, like lls */
+    {"C", ARR_DCt, rule_gen_mat, C_X, 0, 0, 0, ARR_NONE, 1, G_GEN, nullptr, "x"},
+    {"D", ARR_DCt, rule_gen_mat, C_U, 0, 0, 0, ARR_NONE, 1, G_GEN, nullptr, "u"},
+    {"Zl", ARR_Zz, rule_penalty, C_NONE, 0, 0, 0, ARR_NONE, 1, G_DIAG, "sl", nullptr, 0.5},
+    {"Zu", ARR_Zz, rule_penalty, C_NONE, 1, 0, 0, ARR_NONE, 1, G_DIAG, "su", nullptr, 0.5},
+    /* (the seed of zl / zu is the gradient of the slack penalty: the slack part of the stationarity residual, indexed like sl / su) */
+    {"zl", ARR_Zz, rule_penalty, C_NONE, 0, 1, 0, ARR_rgs, 1, G_VEC, "sl"},
+    {"zu", ARR_Zz, rule_penalty, C_NONE, 1, 1, 0, ARR_rgs, 1, G_VEC, "su"},
+    {"u", ARR_ux, rule_var, C_U},
+    {"x", ARR_ux, rule_var, C_X},
+    {"sl", ARR_sv, rule_slack, C_NONE, 0},
+    {"su", ARR_sv, rule_slack, C_NONE, 1},
+    {"pi", ARR_pi, rule_dyn_vec, C_NONE, 0, 1, F_DYN},
+    {"lam", ARR_lam, rule_ct_all},
+    {"t", ARR_t, rule_ct_all},
+    {"ric_L", ARR_Lf, rule_fact_mat},
+    {"ric_l", ARR_lf, rule_fact_vec},
+    /* residual vectors of the last ocp_qp_gpu_batch_res_compute -- the element rule of the quantity each belongs to: res_g [u; x],
+     * res_gs [sl; su], res_b like pi (but in slot k), res_d and res_m like lam */
+    {"res_g", ARR_res_g, rule_fact_vec, C_NONE, 0, 0, F_RES},
+    {"res_gs", ARR_res_gs, rule_slack_both, C_NONE, 0, 0, F_RES},
+    {"res_b", ARR_res_b, rule_dyn_vec, C_NONE, 0, 0, F_DYN | F_RES},
+    {"res_d", ARR_res_d, rule_ct_all, C_NONE, 0, 0, F_RES},
+    {"res_m", ARR_res_m, rule_ct_all, C_NONE, 0, 0, F_RES},
+};
+
+/* the one place a field name is compared */
+const FieldRow *field_row(const char *name)
+{
+    for (const FieldRow &r : k_fields) if (!strcmp(name, r.name)) return &r;
+    return nullptr;
+}
+
+/* a batch's answer for (field, stage): the data itself, the seed seed_<name> or the direction sens_<name> */
+enum FieldUse { USE_DATA, USE_SEED, USE_SENS };
+struct FieldRef
+{
+    const FieldRow *row = nullptr;
+    int k = 0, len = -1;
+    Arr arr = ARR_NONE, arr2 = ARR_NONE;
+    std::vector<int> map, map2; /* element of arr (arr2) per entry, -1: none; bit positions for a mask */
+    bool mask() const { return row->flags & F_MASK; }
+};
+
+/* Returns the field length; -1: no such field, not at this stage, or not in this use */
+int field_resolve(const ocp_qp_gpu_batch *b, const FieldRow *r, int k, FieldUse use, FieldRef &s)
+{
+    s = FieldRef();
+    s.row = r; s.k = k;
+    if (!r || k < 0 || k > b->N || ((r->flags & F_DYN) && k == b->N)) return -1;
+    s.arr = use == USE_SEED ? r->seed : use == USE_SENS ? direction_of(r->arr) : r->arr;
+    if (s.arr == ARR_NONE && !(use == USE_DATA && s.mask())) return -1;
+    const FieldCtx c(b, k);
+    (s.arr == ARR_rgs ? rule_slack : r->rule)(c, *r, s.map);
+    if (r->flags & F_VALUE)
+    {
+        /* equality-flagged x bounds: the bound value is the value of the variable, its seed the derivative of the variable */
+        s.arr2 = use == USE_SEED ? ARR_sfix : ARR_ux;
+        s.map2.assign(c.nbx, -1);
+        for (int ob : b->idxe[k])
+            if (ob >= c.nbu && ob < c.nbu + c.nbx) s.map2[ob - c.nbu] = k * c.n + c.pv(b->idxb[k][ob]);
+    }
+    return s.len = (int) s.map.size();
+}
+
+/* a map whose lower triangle (column-major, dim x dim) is filled: the upper one refers to the mirrored element */
+void mirror_lower(std::vector<int> &map, int dim)
+{
+    for (int c = 0; c < dim; c++) for (int r = 0; r < c; r++) map[c * dim + r] = map[r * dim + c];
 }
 
 int *upload_map(ocp_qp_gpu_batch *b, const std::vector<int> &map)
@@ -1357,22 +1480,12 @@ try
     int rc = 0;
     const double *src = nullptr;
     int src_len = -1;
+    const FieldRow *row = field_row(f);
+    if (row && (row->flags & F_RES)) row = nullptr; /* (read only) */
     for (int k = k0; k <= k1; k++)
     {
-        std::vector<int> map, map2;
-        GArr arr = {nullptr, 0, 0}, arr2 = {nullptr, 0, 0};
-        const size_t flen = strlen(f);
-        if (flen > 5 && !strcmp(f + flen - 5, "_mask"))
-        {
-            const int len = mask_bits(b, f, k, map);
-            if (len < 0) { rc = -1; break; }
-            if (len == 0) continue;
-            if (src_len != len) { src = stage_in(b, data, (size_t) b->B * len, is_device); src_len = len; }
-            int *dm = upload_map(b, map);
-            hipLaunchKernelGGL(gqp::k_setmask, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, b->D.amask, k, b->fam.AW);
-            continue;
-        }
-        const int len = field_map(b, f, k, map, &arr, &map2, &arr2);
+        FieldRef s;
+        const int len = field_resolve(b, row, k, USE_DATA, s);
         if (len < 0)
         {
             if (stage < 0) continue; /* field absent at this stage (e.g. A at N) */
@@ -1381,13 +1494,18 @@ try
         }
         if (len == 0) continue;
         if (src_len != len) { src = stage_in(b, data, (size_t) b->B * len, is_device); src_len = len; }
-        int *dm = upload_map(b, map);
-        b->held.data_written(arr.p == b->D.BAt.p, arr.p == b->D.RSQ.p); /* fields A, B / Q, R, S: stored verdicts are of older data */
-        hipLaunchKernelGGL(gqp::k_scatter, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, arr);
-        if (arr2.p)
+        int *dm = upload_map(b, s.map);
+        if (s.mask())
         {
-            dm = upload_map(b, map2);
-            hipLaunchKernelGGL(gqp::k_scatter, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, arr2);
+            hipLaunchKernelGGL(gqp::k_setmask, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, b->D.amask, k, b->fam.AW);
+            continue;
+        }
+        b->held.data_written(s.arr == ARR_BAt, s.arr == ARR_RSQ); /* a writer of [B A]' / RSQ: stored verdicts are of older data */
+        hipLaunchKernelGGL(gqp::k_scatter, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, arr_of(b, s.arr));
+        if (s.arr2 != ARR_NONE)
+        {
+            dm = upload_map(b, s.map2);
+            hipLaunchKernelGGL(gqp::k_scatter, dim3(grid), dim3(64), 0, b->stream, src, b->B, len, dm, arr_of(b, s.arr2));
         }
     }
     HIPCHK(hipEventRecord(e1, b->stream));
@@ -2259,7 +2377,6 @@ static void polish_pass(ocp_qp_gpu_batch *b, Prof &prof, hipStream_t s)
 /* Sub-batches (SubRole): creation, option hand-down, load and store exist once, here.  What differs per role stays with the callers:
  * how the list is built, n_active and the statistics rows of the levels, the order inside a sensitivity slice, the scalars a
  * ric_alg 0 solve reports */
-typedef GArr GqpDev::*GqpArrMember;
 /* arrays that define a QP instance and its iterate (everything else is recomputed) */
 static const std::vector<GqpArrMember> g_state_arrays = {&GqpDev::BAt, &GqpDev::bvec, &GqpDev::RSQ, &GqpDev::rq, &GqpDev::dvec, &GqpDev::DCt,
                                                          &GqpDev::Zz, &GqpDev::ux, &GqpDev::sv, &GqpDev::pi, &GqpDev::lam, &GqpDev::t};
@@ -2684,51 +2801,28 @@ try
         return -1;
     }
     if (sens_begin(b)) return -1;
-    const char *base = f + 5;
-    std::vector<int> map, map2;
-    GArr arr = {nullptr, 0, 0}, arr2 = {nullptr, 0, 0};
-    const int len = field_map(b, base, k, map, &arr, &map2, &arr2);
-    double sign = 1.0;
-    GArr dst = {nullptr, 0, 0};
-    if (len >= 0)
-    {
-        if (arr.p == b->D.rq.p) dst = b->D.rg;
-        else if (arr.p == b->D.bvec.p) dst = b->D.rb;
-        else if (arr.p == b->D.dvec.p) { dst = b->D.rd; sign = (base[0] == 'l' && base[1] != 'u') || !strcmp(base, "lls") ? -1.0 : 1.0; }
-        else if (!strcmp(base, "zl") || !strcmp(base, "zu"))
-        {
-            /* gradient of the slack penalty: the slack part of the stationarity residual, indexed like sl / su */
-            dst = b->D.rgs;
-            const GqpStage &S = b->st[k];
-            for (int j = 0; j < len; j++) map[j] = S.o_s + (base[1] == 'u' ? S.ns : 0) + j;
-        }
-    }
-    if (len < 0 || !dst.p)
+    FieldRef s;
+    const int len = field_resolve(b, field_row(f + 5), k, USE_SEED, s);
+    if (len < 0)
     {
         fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_sens_set: %s is not a seed of this stage (seeds: seed_q seed_r seed_zl seed_zu seed_b "
                         "seed_lbu seed_ubu seed_lbx seed_ubx seed_lg seed_ug seed_lls seed_lus)\n", f);
         return -1;
     }
     if (len == 0) return 0;
-    if (!strcmp(base, "lus")) sign = -1.0; /* su >= lus is a LOWER bound of the slack, like lls */
     std::vector<double> h((size_t) b->B * len);
-    for (size_t e = 0; e < h.size(); e++) h[e] = sign * data[e];
+    for (size_t e = 0; e < h.size(); e++) h[e] = s.row->sign * data[e];
     const double *src = stage_in(b, h.data(), h.size(), 0);
-    int *dm = upload_map(b, map);
-    hipLaunchKernelGGL(gqp::k_scatter, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, src, b->B, len, dm, dst);
+    int *dm = upload_map(b, s.map);
+    hipLaunchKernelGGL(gqp::k_scatter, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, src, b->B, len, dm, arr_of(b, s.arr));
     HIPCHK(hipStreamSynchronize(b->stream));
-    if (arr2.p)
+    /* equality-flagged bounds: the seed of the bound is the derivative of the variable itself */
+    if (std::any_of(s.map2.begin(), s.map2.end(), [](int m) { return m >= 0; }))
     {
-        /* equality-flagged bounds: the seed of the bound is the derivative of the variable itself */
-        bool any = false;
-        for (int &m : map2) { if (m >= 0) any = true; }
-        if (any)
-        {
-            src = stage_in(b, data, (size_t) b->B * len, 0);
-            dm = upload_map(b, map2);
-            hipLaunchKernelGGL(gqp::k_scatter, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, src, b->B, len, dm, b->sfix);
-            HIPCHK(hipStreamSynchronize(b->stream));
-        }
+        src = stage_in(b, data, (size_t) b->B * len, 0);
+        dm = upload_map(b, s.map2);
+        hipLaunchKernelGGL(gqp::k_scatter, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, src, b->B, len, dm, arr_of(b, s.arr2));
+        HIPCHK(hipStreamSynchronize(b->stream));
     }
     return 0;
 }
@@ -2812,74 +2906,26 @@ try
 {
     HIPCHK(hipSetDevice(b->device));
     finalize_structure(b);
-    std::vector<int> map;
-    GArr arr = {nullptr, 0, 0};
     if (b->factor_stale && !strncmp(f, "ric_", 4)) refactor_at_solution(b);
+    if (!strncmp(f, "res_", 4) && !b->R.nrm) { fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_get: %s before ocp_qp_gpu_batch_res_compute\n", f); return -1; }
     /* sensitivities: the direction arrays of the last ocp_qp_gpu_batch_sens_solve */
     const bool is_sens = !strncmp(f, "sens_", 5);
-    {
-        const size_t flen = strlen(f);
-        if (flen > 5 && !strcmp(f + flen - 5, "_mask"))
-        {
-            /* activity of the sides as 1.0 / 0.0 (equality-flagged rows: 1.0) */
-            const int mlen = mask_bits(b, f, k, map);
-            if (mlen < 0) { fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_get: field %s not available at stage %d\n", f, k); return -1; }
-            if (mlen == 0) return 0;
-            const size_t mcnt = (size_t) b->B * mlen;
-            double *mdst = stage_out(b, data, mcnt, is_device);
-            int *dmm = upload_map(b, map);
-            hipLaunchKernelGGL(gqp::k_getmask, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, mdst, b->B, mlen, dmm, b->D.amask, k, b->fam.AW);
-            stage_out_done(b, data, mcnt, is_device);
-            return 0;
-        }
-    }
-    int len;
-    if (!strncmp(f, "res_", 4))
-    {
-        /* residual vectors of the last ocp_qp_gpu_batch_res_compute: res_g ([u; x]), res_gs ([sl; su]), res_b, res_d,
-         * res_m -- same element maps as the quantity each residual belongs to */
-        if (!b->R.nrm) { fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_get: %s before ocp_qp_gpu_batch_res_compute\n", f); return -1; }
-        const char *like = !strcmp(f, "res_g") ? "ric_l" : !strcmp(f, "res_b") ? "pi" : !strcmp(f, "res_d") || !strcmp(f, "res_m") ? "lam" : nullptr;
-        if (!strcmp(f, "res_gs"))
-        {
-            len = 2 * b->st[k].ns;
-            for (int j = 0; j < len; j++) map.push_back(b->st[k].o_s + j);
-            arr = b->R.gs;
-        }
-        else if (like)
-        {
-            len = field_map(b, like, k, map, &arr);
-            if (!strcmp(f, "res_b")) for (int &m : map) m -= b->fam.ks()->NX; /* pi lives in slot k+1, res_b in slot k */
-            arr = !strcmp(f, "res_g") ? b->R.g : !strcmp(f, "res_b") ? b->R.b : !strcmp(f, "res_d") ? b->R.d : b->R.m;
-        }
-        else len = -1;
-    }
-    else len = field_map(b, is_sens ? f + 5 : f, k, map, &arr);
-    if (len > 0 && (!strcmp(f, "Q") || !strcmp(f, "R")))
-    {
-        /* the packed lower triangle holds the matrix: mirror it for the reader */
-        const int dim = f[0] == 'Q' ? b->nx[k] : b->nu[k];
-        for (int c = 0; c < dim; c++) for (int r = 0; r < c; r++) map[c * dim + r] = map[r * dim + c];
-    }
-    if (is_sens && len >= 0)
-    {
-        if (arr.p == b->D.ux.p) arr = b->D.dux;
-        else if (arr.p == b->D.sv.p) arr = b->D.dsv;
-        else if (arr.p == b->D.pi.p) arr = b->D.dpi;
-        else if (arr.p == b->D.lam.p) arr = b->D.dlam;
-        else if (arr.p == b->D.t.p) arr = b->D.dt;
-        else len = -1;
-    }
+    FieldRef s;
+    const int len = field_resolve(b, field_row(is_sens ? f + 5 : f), k, is_sens ? USE_SENS : USE_DATA, s);
     if (len < 0)
     {
         fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_get: field %s not available at stage %d\n", f, k);
         return -1;
     }
     if (len == 0) return 0;
+    if (s.row->flags & F_SYM) mirror_lower(s.map, FieldCtx(b, k).nvar(s.row->cls)); /* the reader gets the whole matrix */
     const size_t cnt = (size_t) b->B * len;
     double *dst = stage_out(b, data, cnt, is_device);
-    int *dm = upload_map(b, map);
-    hipLaunchKernelGGL(gqp::k_gather, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, dst, b->B, len, dm, arr);
+    int *dm = upload_map(b, s.map);
+    if (s.mask()) /* activity of the sides as 1.0 / 0.0 (equality-flagged rows: 1.0) */
+        hipLaunchKernelGGL(gqp::k_getmask, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, dst, b->B, len, dm, b->D.amask, k, b->fam.AW);
+    else
+        hipLaunchKernelGGL(gqp::k_gather, dim3((b->B + 63) / 64), dim3(64), 0, b->stream, dst, b->B, len, dm, arr_of(b, s.arr));
     stage_out_done(b, data, cnt, is_device);
     return 0;
 }
@@ -3151,25 +3197,26 @@ static const char *const k_bulk_vec_fields[] = {"b", "q", "r", "lbu", "ubu", "lb
  * interfaces/acados_template/acados_template/c_templates_tera/acados_solver.in.c:3292-3337) */
 static const char *const k_seed_fields[] = {"r", "q", "zl", "zu", "b", "lbu", "lbx", "lg", "ubu", "ubx", "ug", "lls", "lus"};
 
-/* The kinds of blob.  A new kind is a row here (+ its BlobKind): the field list in blob order, the prefix its segment names carry
- * in the offset queries, whether its *_mask fields are bit segments of the activity words (k_bulk_masks / k_bulk_masks_get) and
- * whether it is READ through a table pair of its own (d_arr_g / d_elem_g; else through the pair it is written by).  What one
- * blob entry refers to is the element rule of blob_map, applied to the fields of the walk (blob_fields): a second table over an
- * existing kind is another rule there */
+/* The kinds of blob.  A new kind is a row here (+ its BlobKind): the field list in blob order (names of k_fields), the prefix its
+ * segment names carry in the offset queries with the use of the fields that goes with it, and whether it is READ through a table
+ * pair of its own (d_arr_g / d_elem_g; else through the pair it is written by).  What one blob entry refers to is the field's row
+ * of k_fields (field_resolve), applied to the fields of the walk (blob_fields): a mask field is a bit segment of the activity words
+ * (k_bulk_masks / k_bulk_masks_get), a kind that lists A / B or Q / R / S leaves no stored held verdict standing when it is
+ * scattered (BulkMap::writes_dyn / writes_hess) */
 struct BlobDesc
 {
     const char *const *fields;
     int nf;
     const char *prefix;
-    bool masks, read_map;
-    bool matrices; /* the kind carries A / B / Q / R / S: scattering it leaves no stored held-dynamics verdict standing */
+    FieldUse use;
+    bool read_map;
 };
-#define GQP_BLOB(fields, prefix, masks, read_map, matrices) {fields, (int) (sizeof(fields) / sizeof(fields[0])), prefix, masks, read_map, matrices}
+#define GQP_BLOB(fields, prefix, use, read_map) {fields, (int) (sizeof(fields) / sizeof(fields[0])), prefix, use, read_map}
 static const BlobDesc k_blobs[BLOB_KINDS] = {
-    /* BLOB_IN   */ GQP_BLOB(k_bulk_in_fields, "", true, true, true),
-    /* BLOB_OUT  */ GQP_BLOB(k_bulk_out_fields, "", false, false, false),
-    /* BLOB_VEC  */ GQP_BLOB(k_bulk_vec_fields, "", true, false, false),
-    /* BLOB_SEED */ GQP_BLOB(k_seed_fields, "seed_", false, false, false),
+    /* BLOB_IN   */ GQP_BLOB(k_bulk_in_fields, "", USE_DATA, true),
+    /* BLOB_OUT  */ GQP_BLOB(k_bulk_out_fields, "", USE_DATA, false),
+    /* BLOB_VEC  */ GQP_BLOB(k_bulk_vec_fields, "", USE_DATA, false),
+    /* BLOB_SEED */ GQP_BLOB(k_seed_fields, "seed_", USE_SEED, false),
 };
 
 /* the public integers: `output` of _bulk_len / _bulk_offset is 0 for the input blob, 2 for its vector part and anything else for
@@ -3180,35 +3227,29 @@ static BlobKind blob_kind(int v, bool has_out = true)
     return v && has_out ? BLOB_OUT : BLOB_IN;
 }
 
-/* one field of one stage as the walk hands it to the element rules */
-struct BlobField
+/* a segment of the field s, its entries referring to element m[e] of `slot` (m[e] < 0: to nothing) */
+static void blob_segment_add(BulkMap &M, const std::string &name, const FieldRef &s, int slot, const std::vector<int> &m)
 {
-    const char *f;
-    int k, len;
-    bool is_mask;
-    std::vector<int> map, map2; /* element of arr (arr2) per entry, -1: none; bit positions for a mask */
-    GArr arr = {nullptr, 0, 0}, arr2 = {nullptr, 0, 0};
-};
-
-static void blob_open_segment(BulkMap &M, const std::string &name, int k, int len)
-{
-    M.fields.push_back(name); M.seg_stage.push_back(k); M.seg_off.push_back((int) M.arr.size()); M.seg_len.push_back(len);
+    M.fields.push_back(name); M.seg_row.push_back((int) (s.row - k_fields)); M.seg_stage.push_back(s.k);
+    M.seg_off.push_back((int) M.arr.size()); M.seg_len.push_back(s.len);
+    for (int el : m) { M.arr.push_back(el >= 0 ? slot : -1); M.elem.push_back(el >= 0 ? el : 0); }
 }
 
 /* the layout of every kind: stage-major, the kind's field order, fields of length 0 at a stage skipped */
-static void blob_fields(ocp_qp_gpu_batch *b, const BlobDesc &K, const std::function<void(const BlobField &)> &visit)
+static void blob_fields(ocp_qp_gpu_batch *b, const BlobDesc &K, const std::function<void(const FieldRef &)> &visit)
 {
+    std::vector<const FieldRow *> rows;
+    for (int fi = 0; fi < K.nf; fi++)
+    {
+        rows.push_back(field_row(K.fields[fi]));
+        if (rows.back()) continue;
+        fprintf(stderr, "\nerror: acados_amd: blob field %s is not a field of k_fields\n", K.fields[fi]);
+        throw gqp_hip_failure{-1};
+    }
+    FieldRef s;
     for (int k = 0; k <= b->N; k++)
-        for (int fi = 0; fi < K.nf; fi++)
-        {
-            BlobField s;
-            s.f = K.fields[fi]; s.k = k;
-            const size_t flen = strlen(s.f);
-            s.is_mask = K.masks && flen > 5 && !strcmp(s.f + flen - 5, "_mask");
-            if (s.is_mask) s.len = mask_bits(b, s.f, k, s.map);
-            else s.len = field_map(b, s.f, k, s.map, &s.arr, &s.map2, &s.arr2);
-            if (s.len > 0) visit(s);
-        }
+        for (const FieldRow *r : rows)
+            if (field_resolve(b, r, k, K.use, s) > 0) visit(s);
 }
 
 /* the map of a kind, built on its first use */
@@ -3219,85 +3260,44 @@ static BulkMap &blob_map(ocp_qp_gpu_batch *b, BlobKind kind) /* throws gqp_hip_f
     if (M.built) return M;
     finalize_structure(b);
     const BlobDesc &K = k_blobs[kind];
-    const GqpDev &D = b->D;
     if (kind == BLOB_SEED)
     {
-        /* entry -> residual array (0 rg, 1 rgs, 2 rb, 3 rd: the table of _sens_set_bulk), element, sign there, slot in sfix */
+        /* entry -> residual array (slot of k_seed_arrays: the table of _sens_set_bulk), element, sign there, slot in sfix */
         std::vector<int> sgn, elem2;
-        blob_fields(b, K, [&](const BlobField &s) {
-            blob_open_segment(M, K.prefix + std::string(s.f), s.k, s.len);
-            const GqpStage &S = b->st[s.k];
-            const bool slack_grad = s.f[0] == 'z';
-            int a = -1, sg = 1;
-            if (slack_grad) a = 1;
-            else if (s.arr.p == D.rq.p) a = 0;
-            else if (s.arr.p == D.bvec.p) a = 2;
-            else if (s.arr.p == D.dvec.p) { a = 3; sg = (s.f[0] == 'l') ? -1 : 1; } /* lbu lbx lg lls lus: lower bounds */
+        blob_fields(b, K, [&](const FieldRef &s) {
+            blob_segment_add(M, K.prefix + std::string(s.row->name), s, slot_of(k_seed_arrays, s.arr), s.map);
             for (int e = 0; e < s.len; e++)
             {
-                int el = s.map[e];
-                if (slack_grad) el = S.o_s + (s.f[1] == 'u' ? S.ns : 0) + e; /* rgs is indexed like sv */
-                M.arr.push_back(el >= 0 ? a : -1); M.elem.push_back(el >= 0 ? el : 0); sgn.push_back(sg);
-                elem2.push_back(s.arr2.p && s.map2[e] >= 0 ? s.map2[e] : -1);
+                sgn.push_back(s.row->sign);
+                elem2.push_back(s.arr2 != ARR_NONE && s.map2[e] >= 0 ? s.map2[e] : -1);
             }
         });
         M.d_sgn = upload(b, sgn); M.d_elem2 = upload(b, elem2);
     }
     else
     {
-        /* entry -> array of the table below and element in it; a mask entry -> (position, stage, bit) */
-        const GArr table[16] = {D.BAt, D.bvec, D.RSQ, D.rq, D.dvec, D.DCt, D.Zz, D.ux, D.sv, D.pi, D.lam, D.t,
-                                {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}, {nullptr, 0, 0}};
-        for (int q = 0; q < 16; q++) M.T.a[q] = table[q];
-        auto table_index = [&](const GArr &a) {
-            for (int q = 0; q < 12; q++) if (table[q].p == a.p) return q;
-            return -1;
-        };
+        /* entry -> array (slot of k_state_arrays) and element in it; a mask entry -> (position, stage, bit) */
+        table_fill(b, M.T, k_state_arrays);
         std::vector<int> moff, mstage, mbit, arr_g, elem_g;
-        blob_fields(b, K, [&](const BlobField &s) {
-            blob_open_segment(M, K.prefix + std::string(s.f), s.k, s.len);
-            const int o = (int) M.arr.size();
-            for (int e = 0; e < s.len; e++)
-            {
-                if (s.is_mask)
-                {
-                    moff.push_back(o + e); mstage.push_back(s.k); mbit.push_back(s.map[e]);
-                    M.arr.push_back(-1); M.elem.push_back(0);
-                }
-                else
-                {
-                    M.arr.push_back(s.map[e] >= 0 ? table_index(s.arr) : -1); M.elem.push_back(s.map[e] >= 0 ? s.map[e] : 0);
-                }
-            }
-            if (K.read_map)
-            {
-                const bool sym = !strcmp(s.f, "Q") || !strcmp(s.f, "R");
-                const int dim = sym ? (s.f[0] == 'Q' ? b->nx[s.k] : b->nu[s.k]) : 0;
-                for (int e = 0; e < s.len; e++)
-                {
-                    int a = M.arr[o + e], el = M.elem[o + e];
-                    if (sym && a < 0)
-                    {
-                        const int r = e % dim, c = e / dim;       /* column-major, r < c here */
-                        const int m = s.map[r * dim + c];         /* element (c, r) */
-                        if (m >= 0) { a = table_index(s.arr); el = m; }
-                    }
-                    arr_g.push_back(a); elem_g.push_back(el);
-                }
-            }
-            if (s.arr2.p)
-            {
+        blob_fields(b, K, [&](const FieldRef &s) {
+            const int o = (int) M.arr.size(), slot = slot_of(k_state_arrays, s.arr);
+            blob_segment_add(M, K.prefix + std::string(s.row->name), s, slot, s.mask() ? std::vector<int>(s.len, -1) : s.map);
+            if (s.mask())
+                for (int e = 0; e < s.len; e++) { moff.push_back(o + e); mstage.push_back(s.k); mbit.push_back(s.map[e]); }
+            M.writes_dyn |= s.arr == ARR_BAt; M.writes_hess |= s.arr == ARR_RSQ;
+            if (s.arr2 != ARR_NONE)
                 /* equality-flagged x bounds also define the value of the variable: a second, hidden
                  * segment that re-reads the same blob entries is not possible, so those entries are
                  * written through a duplicate segment placed right after (the caller's blob carries
                  * lbx twice: once as bound, once as value -- see ocp_qp_gpu_batch_bulk_offset) */
-                blob_open_segment(M, std::string(s.f) + "#value", s.k, s.len);
-                for (int e = 0; e < s.len; e++)
-                {
-                    M.arr.push_back(s.map2[e] >= 0 ? table_index(s.arr2) : -1); M.elem.push_back(s.map2[e] >= 0 ? s.map2[e] : 0);
-                    if (K.read_map) { arr_g.push_back(M.arr.back()); elem_g.push_back(M.elem.back()); }
-                }
-            }
+                blob_segment_add(M, std::string(s.row->name) + "#value", s, slot_of(k_state_arrays, s.arr2), s.map2);
+            if (!K.read_map) return;
+            /* the read map: what was just added, with the strict upper triangle of Q / R read from the mirrored element */
+            arr_g.insert(arr_g.end(), M.arr.begin() + o, M.arr.end()); elem_g.insert(elem_g.end(), M.elem.begin() + o, M.elem.end());
+            if (!(s.row->flags & F_SYM)) return;
+            std::vector<int> g = s.map;
+            mirror_lower(g, FieldCtx(b, s.k).nvar(s.row->cls));
+            for (int e = 0; e < s.len; e++) { arr_g[o + e] = g[e] >= 0 ? slot : -1; elem_g[o + e] = g[e] >= 0 ? g[e] : 0; }
         });
         M.nm = (int) moff.size();
         if (K.read_map) { M.d_arr_g = upload(b, arr_g); M.d_elem_g = upload(b, elem_g); }
@@ -3363,9 +3363,7 @@ static void bulk_scatter_launch(ocp_qp_gpu_batch *b, const double *src, int len,
  * the kind has mask entries, the launch that turns them into the activity words.  No wait, no timing: those are the caller's */
 static void blob_scatter(ocp_qp_gpu_batch *b, BulkMap &M, const double *src)
 {
-    /* the kinds that carry matrices (BlobDesc::matrices) leave no stored verdict standing */
-    const bool matrices = k_blobs[&M - b->blob].matrices;
-    b->held.data_written(matrices, matrices);
+    b->held.data_written(M.writes_dyn, M.writes_hess);
     bulk_scatter_launch(b, src, M.len, M);
     if (M.nm)
         hipLaunchKernelGGL(gqp::k_bulk_masks, dim3((b->B + 63) / 64, (b->N + 1 + GQP_MASK_SPC - 1) / GQP_MASK_SPC), dim3(64), 0, b->stream, src, b->B, M.len, M.d_moff,
@@ -3559,8 +3557,8 @@ static void blob_get_out(ocp_qp_gpu_batch *b, double *blob, int is_device, bool 
 {
     BulkMap &M = blob_map(b, BLOB_OUT);
     gqp::GArrTable T = M.T;
-    const GqpDev &D = b->D;
-    if (directions) { T.a[7] = D.dux; T.a[8] = D.dsv; T.a[9] = D.dpi; T.a[10] = D.dlam; T.a[11] = D.dt; }
+    if (directions)
+        for (Arr a : {ARR_ux, ARR_sv, ARR_pi, ARR_lam, ARR_t}) T.a[slot_of(k_state_arrays, a)] = arr_of(b, direction_of(a));
     const size_t cnt = (size_t) b->B * M.len;
     bulk_gather_launch(b, stage_out(b, blob, cnt, is_device), M.len, M.d_arr_g, M.d_elem_g, T);
     stage_out_done(b, blob, cnt, is_device);
@@ -3596,9 +3594,7 @@ try
     const int len = M.len;
     if (sens_begin(b)) return -1; /* zeroes the seed arrays, factorises at the solution where the sweeps run in place */
     if (len == 0) return 0;
-    const GqpDev &D = b->D;
-    const GArr table[5] = {D.rg, D.rgs, D.rb, D.rd, b->sfix};
-    for (int q = 0; q < 16; q++) M.T.a[q] = q < 5 ? table[q] : GArr{nullptr, 0, 0};
+    table_fill(b, M.T, k_seed_arrays);
     const double *src = stage_in(b, blob, (size_t) b->B * len, is_device);
     const dim3 grid((b->B + 63) / 64, (len + 255) / 256), block(64);
     hipLaunchKernelGGL(gqp::k_bulk_scatter_seed, grid, block, 0, b->stream, src, b->B, len, M.d_arr, M.d_elem, M.d_sgn, M.d_elem2, M.T);
@@ -3623,99 +3619,94 @@ static void grad_build(ocp_qp_gpu_batch *b)
     const BulkMap &Mi = blob_map(b, BLOB_IN), &Mo = blob_map(b, BLOB_OUT);
     const int len = Mi.len, olen = Mo.len;
     const int N = b->N, NX = b->fam.ks()->NX, NU = b->fam.ks()->NU, n = NX + NU, NP = n * (n + 1) / 2;
-    auto ob = [&](const char *f, int k) { int l = 0; const int o = blob_segment(Mo, f, k, &l); return l > 0 ? o : -1; };
-    /* output blob: gather map renumbered to the kernel's tables, activity gates, cotangent destinations */
+    auto ob = [&](const char *f, int k, int *len = nullptr) {
+        int l = 0;
+        const int o = f ? blob_segment(Mo, f, k, &l) : -1;
+        if (len) *len = l;
+        return l > 0 ? o : -1;
+    };
+    /* output blob: gather map renumbered to the kernel's table, activity gates, cotangent destinations */
     std::vector<int> oarr(olen, -1), oelem = Mo.elem, ogate(olen, -1), ckind(olen, 0), celem(olen, 0);
-    for (int e = 0; e < olen; e++) oarr[e] = Mo.arr[e] >= 7 && Mo.arr[e] <= 11 ? Mo.arr[e] - 7 : -1;
+    for (int e = 0; e < olen; e++) oarr[e] = Mo.arr[e] >= 0 ? slot_of(k_grad_arrays, k_state_arrays[Mo.arr[e]]) : -1;
     for (size_t q = 0; q < Mo.fields.size(); q++)
     {
-        const std::string &f = Mo.fields[q];
         const int k = Mo.seg_stage[q], o = Mo.seg_off[q], l = Mo.seg_len[q];
-        const GqpStage &S = b->st[k];
-        const int nbg = S.nb + S.ng;
+        const FieldCtx c(b, k);
         for (int e = 0; e < l; e++)
-        {
-            if (f == "u" || f == "x")
+            switch (k_fields[Mo.seg_row[q]].arr)
             {
-                const int pv = oelem[o + e] - k * n;
-                ckind[o + e] = ((S.emask >> pv) & 1) ? 3 : 1;
+            case ARR_ux: /* to rg, but for a fixed variable */
+                ckind[o + e] = ((c.S.emask >> (oelem[o + e] - k * n)) & 1) ? 3 : 1;
                 celem[o + e] = oelem[o + e];
-            }
-            else if (f == "sl" || f == "su") { ckind[o + e] = 2; celem[o + e] = oelem[o + e]; }
-            if (f == "lam" || f == "t")
+                break;
+            case ARR_sv: /* to rgs */
+                ckind[o + e] = 2;
+                celem[o + e] = oelem[o + e];
+                break;
+            case ARR_lam:
+            case ARR_t:
             {
-                const int bit = oelem[o + e] - S.o_ct;
+                const int bit = oelem[o + e] - c.S.o_ct;
                 ogate[o + e] = (k * b->fam.AW + bit / 64) * 64 + bit % 64;
-                if (e < 2 * nbg)
-                {
-                    const int r = e % nbg; /* original row order: box rows, then general rows */
-                    if (r < S.nb && std::find(b->idxe[k].begin(), b->idxe[k].end(), r) != b->idxe[k].end()) ogate[o + e] = -2;
-                }
+                if (e < 2 * c.nbg && c.eq(e % c.nbg)) ogate[o + e] = -2; /* (the sides in the original row order) */
+                break;
             }
-        }
+            default: break;
+            }
     }
+    const int t_hess = slot_of(k_grad_arrays, ARR_RSQ), t_dyn = slot_of(k_grad_arrays, ARR_BAt), t_gen = slot_of(k_grad_arrays, ARR_DCt),
+              t_cot = slot_of(k_grad_arrays, ARR_cot);
     /* input blob: one op per entry */
     std::vector<gqp::GradOp> ops(len, gqp::GradOp{0, 0, -1, 0, 0.0});
     std::vector<gqp::GradTerm> terms;
     for (size_t q = 0; q < Mi.fields.size(); q++)
     {
-        const std::string &f = Mi.fields[q];
+        const FieldRow &r = k_fields[Mi.seg_row[q]];
         const int k = Mi.seg_stage[q], o = Mi.seg_off[q], l = Mi.seg_len[q];
-        const GqpStage &S = b->st[k];
-        const int nx = b->nx[k], nu = b->nu[k], nx1 = k < N ? b->nx[k + 1] : 0, ng = S.ng, nb = S.nb, nbg = nb + ng, ns = S.ns;
-        const int ou = ob("u", k), ox = ob("x", k), osl = ob("sl", k), osu = ob("su", k), opi = k < N ? ob("pi", k) : -1, olam = ob("lam", k);
-        auto vec = [&](int e, int a, double c) { ops[o + e] = gqp::GradOp{1, a, -1, 0, c}; };
-        auto prod = [&](int e, int a, int a2, int bb, double c) { ops[o + e] = gqp::GradOp{2, a, a2, bb, c}; };
-        auto is_eq = [&](int row) { return std::find(b->idxe[k].begin(), b->idxe[k].end(), row) != b->idxe[k].end(); };
-        const bool bnd = f == "lbu" || f == "ubu" || f == "lbx" || f == "ubx";
-        for (int e = 0; e < l; e++)
+        const FieldCtx c(b, k);
+        const GqpStage &S = c.S;
+        const int nx = c.nx, nu = c.nu, nx1 = c.nx1, ng = c.ng, nb = S.nb, nbg = c.nbg;
+        const int ou = ob("u", k), ox = ob("x", k), opi = k < N ? ob("pi", k) : -1, olam = ob("lam", k);
+        int la = 0; /* the row's own factors: S[] / D[] of the fields ga (la long) and gb */
+        const int oa = ob(r.ga, k, &la), og = ob(r.gb, k);
+        auto vec = [&](int e, int a, double co) { ops[o + e] = gqp::GradOp{1, a, -1, 0, co}; };
+        auto prod = [&](int e, int a, int a2, int bb, double co) { ops[o + e] = gqp::GradOp{2, a, a2, bb, co}; };
+        if (Mi.fields[q] == "lbx#value")
         {
-            if (f == "A") prod(e, opi + e % nx1, -1, ox + e / nx1, 1.0);
-            else if (f == "B") prod(e, opi + e % nx1, -1, ou + e / nx1, 1.0);
-            else if (f == "b") vec(e, opi + e, 1.0);
-            else if (f == "Q") prod(e, ox + e % nx, -1, ox + e / nx, 0.5);
-            else if (f == "R") prod(e, ou + e % nu, -1, ou + e / nu, 0.5);
-            else if (f == "S") prod(e, ou + e % nu, -1, ox + e / nu, 1.0);
-            else if (f == "q") vec(e, ox + e, 1.0);
-            else if (f == "r") vec(e, ou + e, 1.0);
-            else if (bnd)
+            for (int e = 0; e < l; e++)
             {
-                const int row = (f[2] == 'x' ? b->nbu[k] : 0) + e;
-                if (!is_eq(row)) vec(e, olam + (f[0] == 'u' ? nbg : 0) + row, f[0] == 'u' ? -1.0 : 1.0);
-            }
-            else if (f == "lg") vec(e, olam + nb + e, 1.0);
-            else if (f == "ug") vec(e, olam + nbg + nb + e, -1.0);
-            else if (f == "C") prod(e, olam + nbg + nb + e % ng, olam + nb + e % ng, ox + e / ng, 1.0);
-            else if (f == "D") prod(e, olam + nbg + nb + e % ng, olam + nb + e % ng, ou + e / ng, 1.0);
-            else if (f == "Zl") prod(e, osl + e, -1, osl + e, 0.5);
-            else if (f == "Zu") prod(e, osu + e, -1, osu + e, 0.5);
-            else if (f == "zl") vec(e, osl + e, 1.0);
-            else if (f == "zu") vec(e, osu + e, 1.0);
-            else if (f == "lls") vec(e, olam + 2 * nbg + e, 1.0);
-            else if (f == "lus") vec(e, olam + 2 * nbg + ns + e, 1.0);
-            else if (f == "lbx#value")
-            {
-                const int row = b->nbu[k] + e;
-                if (!is_eq(row)) continue;
+                const int row = c.nbu + e;
+                if (!c.eq(row)) continue;
                 /* the value of a fixed variable: its stationarity row applied to the adjoint direction, plus its own cotangent */
-                const int vi = b->idxb[k][row], j = padded_var(b, k, vi);
+                const int vi = b->idxb[k][row], j = c.pv(vi);
                 const int t0 = (int) terms.size();
-                terms.push_back(gqp::GradTerm{13, k * n + j, -1, 0, 1.0});
-                for (int r = 0; r < nu + nx; r++)
+                terms.push_back(gqp::GradTerm{t_cot, k * n + j, -1, 0, 1.0});
+                for (int i = 0; i < nu + nx; i++)
                 {
-                    const int pr = padded_var(b, k, r);
-                    terms.push_back(gqp::GradTerm{10, k * NP + (pr >= j ? PK(pr, j) : PK(j, pr)), r < nu ? ou + r : ox + r - nu, 0, 1.0});
+                    const int pr = c.pv(i);
+                    terms.push_back(gqp::GradTerm{t_hess, k * NP + (pr >= j ? PK(pr, j) : PK(j, pr)), i < nu ? ou + i : ox + i - nu, 0, 1.0});
                 }
-                for (int c = 0; c < nx1; c++) terms.push_back(gqp::GradTerm{11, (k * n + j) * NX + c, opi + c, 0, 1.0});
+                for (int i = 0; i < nx1; i++) terms.push_back(gqp::GradTerm{t_dyn, (k * n + j) * NX + i, opi + i, 0, 1.0});
                 if (vi >= nu && k > 0) terms.push_back(gqp::GradTerm{-1, 0, ob("pi", k - 1) + vi - nu, 0, -1.0});
                 for (int g = 0; g < ng; g++)
                 {
-                    terms.push_back(gqp::GradTerm{12, (S.o_g + g) * n + j, olam + nbg + nb + g, 0, 1.0});
-                    terms.push_back(gqp::GradTerm{12, (S.o_g + g) * n + j, olam + nb + g, 0, -1.0});
+                    terms.push_back(gqp::GradTerm{t_gen, (S.o_g + g) * n + j, olam + nbg + nb + g, 0, 1.0});
+                    terms.push_back(gqp::GradTerm{t_gen, (S.o_g + g) * n + j, olam + nb + g, 0, -1.0});
                 }
                 ops[o + e] = gqp::GradOp{3, t0, (int) terms.size(), 0, 0.0};
             }
+            continue;
         }
+        for (int e = 0; e < l; e++)
+            switch (r.grad)
+            {
+            case G_VEC: vec(e, oa + e, 1.0); break;                                   /* b q r zl zu: the direction of their variable */
+            case G_PROD: prod(e, oa + e % la, -1, og + e / la, r.gc); break;          /* A B Q R S: entry (row of ga, column of gb) */
+            case G_DIAG: prod(e, oa + e, -1, oa + e, r.gc); break;                    /* Zl Zu */
+            case G_GEN: prod(e, olam + nbg + nb + e % ng, olam + nb + e % ng, og + e / ng, 1.0); break; /* C D: upper minus lower side */
+            case G_CT: if (!c.ct_eq(r, e)) vec(e, olam + c.ct_pos(r, e), -r.sign); break; /* a bound: -+ lam^ of its side, the seed's sign reversed */
+            default: break;                                                          /* masks: op 0 */
+            }
     }
     G.len = len;
     G.olen = olen;
@@ -3783,8 +3774,7 @@ try
     double *dst = stage_out(b, grad, cnt, is_device);
     const GqpDev &D = b->D;
     gqp::GArrTable T;
-    const GArr tab[14] = {D.ux, D.sv, D.pi, D.lam, D.t, D.dux, D.dsv, D.dpi, D.dlam, D.dt, D.RSQ, D.BAt, D.DCt, G.cot};
-    for (int q = 0; q < 16; q++) T.a[q] = q < 14 ? tab[q] : GArr{nullptr, 0, 0};
+    table_fill(b, T, k_grad_arrays);
     const int per = (b->B + GQP_GRAD_XCD - 1) / GQP_GRAD_XCD;
     if (G.len)
         GQP_LAUNCH_COOP(gqp::k_data_grad, dim3(per * GQP_GRAD_XCD), dim3(GQP_GRAD_THREADS), G.lds, b->stream, dst, b->B, G.len, G.d_ops, G.d_terms,

@@ -318,3 +318,61 @@ def test_time_pack_grows_once_per_blob(clib):
         print("time_pack increments (s):", grown)
     finally:
         assert L.ocp_qp_gpu_host_unregister(_vp(block)) == 0
+
+
+def _every_structure():
+    from random_qp import random_structure_qp
+    return _structures() + [(f"random_{s}", lambda s=s: random_structure_qp(s)) for s in (0, 1, 8, 11)]
+
+
+@pytest.mark.parametrize("clib", TIERS, indirect=True)
+@pytest.mark.parametrize("make_qp", [pytest.param(m, id=n) for n, m in _every_structure()])
+def test_every_field_through_the_blob_and_the_getter(clib, make_qp):
+    """The element rule of every field, through the blob entries and through the per-field getter, against the documented layout
+    (_expected), on structures with changing dims, equality-flagged rows, general rows and slacks.  Entry e of instance i of the
+    input blob is 1000 (i + 1) + e + 1 (a mask entry (e + i) mod 2), so an entry that lands in another place is seen.
+    (a) after _set_bulk, get(f, k) is the blob's segment (f, k) for every input field and mask; Q and R come back as the symmetric
+        matrix of the segment's lower triangle, lbx_mask / ubx_mask are compared without the equality-flagged rows (always active),
+        the lbx#value segment has no getter;
+    (b) _get_bulk_in returns the blob except in the upper triangles of Q / R, the mask entries of equality-flagged rows and the
+        lbx#value entries of rows that are not equality-flagged;
+    (c) after _set_bulk_out of 500 (i + 1) + e + 1, get(f, k) of u x sl su pi lam t is the segment."""
+    from acados_amd import OcpQpGpuBatch
+    gb = OcpQpGpuBatch.from_qps([make_qp()] * B, _clib=clib)
+    d = _dims(gb)
+    segs, n = _expected(d, IN_FIELDS, value_segment=True)
+    inst = np.arange(B)[:, None]
+    blob = 1000.0 * (inst + 1) + np.arange(n)[None, :] + 1.0
+    free = np.zeros(n, dtype=bool)                       # entries _get_bulk_in need not return as they were sent
+    for (f, k), (o, l) in segs.items():
+        if f.endswith("_mask"):
+            blob[:, o:o + l] = (np.arange(o, o + l)[None, :] + inst) % 2
+            if f in ("lbx_mask", "ubx_mask"):
+                free[o + _eq_rows(gb, d, k)] = True
+        elif f in ("Q", "R"):
+            m = int(round(np.sqrt(l)))
+            free[o:o + l] = np.triu(np.ones((m, m), dtype=bool), 1).reshape(-1, order="F")
+        elif f == "lbx#value":
+            free[o:o + l] = True
+            free[o + _eq_rows(gb, d, k)] = False
+    sent = blob.copy()
+    gb.set_bulk(blob)
+    for (f, k), (o, l) in segs.items():
+        if f == "lbx#value":
+            continue
+        want, got = sent[:, o:o + l], gb.get(f, k)
+        if f in ("Q", "R"):
+            m = int(round(np.sqrt(l)))
+            low = np.tril(want.reshape(B, m, m).transpose(0, 2, 1))          # column-major segment -> [row, column]
+            want = (low + np.tril(low, -1).transpose(0, 2, 1)).transpose(0, 2, 1).reshape(B, l)
+        elif f in ("lbx_mask", "ubx_mask"):
+            keep = np.setdiff1d(np.arange(l), _eq_rows(gb, d, k))
+            want, got = want[:, keep], got[:, keep]
+        assert np.array_equal(got, want), (f, k)
+    back = gb.get_bulk_in()
+    assert np.array_equal(back[:, ~free], sent[:, ~free]), np.argwhere(back[:, ~free] != sent[:, ~free])[:5]
+    osegs, no = _expected(d, OUT_FIELDS)
+    ob = 500.0 * (inst + 1) + np.arange(no)[None, :] + 1.0
+    gb._blob_call(gb._L.ocp_qp_gpu_batch_set_bulk_out, ob, 1, "ocp_qp_gpu_batch_set_bulk_out")
+    for (f, k), (o, l) in osegs.items():
+        assert np.array_equal(gb.get(f, k), ob[:, o:o + l]), (f, k)
