@@ -549,6 +549,18 @@ static __global__ void __launch_bounds__(GQP_KD_THREADS) kd_solve(GqpDev D, GqpO
         }
         __syncthreads();
     }
+    /* multipliers of the equality-flagged rows from stationarity, t = 0 for them (as kb_finalize / kw_finalize recover them; k_finalize
+     * of the general one-instance-per-lane family relies on its factor sweeps for them, and those have not run) */
+    for (int r = tid; r < R; r += NT)
+    {
+        const KdRow q = rows[r];
+        if (!q.fixed || q.var < 0) continue;
+        double a = rw[q.k * n + q.var];
+        if (q.k + 1 < K) for (int c = 0; c < NX; c++) a += GATL(D.BAt, (q.k * n + q.var) * NX + c) * GATL(D.pi, (q.k + 1) * NX + c);
+        if (q.var >= NU) a -= GATL(D.pi, q.k * NX + q.var - NU);
+        GATL(D.lam, q.lo) = a > 0.0 ? a : 0.0; GATL(D.lam, q.up) = a < 0.0 ? -a : 0.0;
+        GATL(D.t, q.lo) = 0.0; GATL(D.t, q.up) = 0.0;
+    }
     if (tid == 0)
     {
         D.status[i] = status; D.iter[i] = it; D.mu[i] = mu; D.alpha[i] = alpha;

@@ -318,6 +318,7 @@ struct ocp_qp_gpu_batch
     int kd_unsupported = 0;
     double *d_kd_ws = nullptr;
     int kd_slice = 0;
+    int full_dense_slice = 0;          /* option "full_dense_slice": instances per kd_solve launch (0: as many as 8 GiB of workspace hold) */
     /* terminal polishing step (option "polish", opt-in: polish_pass below) */
     int polish = 0;
     double polish_ratio = 1e-3;
@@ -431,6 +432,15 @@ T *dalloc(ocp_qp_gpu_batch *b, size_t cnt)
     b->allocs.push_back(p);
     b->bytes += bytes;
     return (T *) p;
+}
+
+/* gives back ONE array of dalloc (bytes as it was asked for) that is about to be replaced by another size */
+void dfree(ocp_qp_gpu_batch *b, void *p, size_t bytes)
+{
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->allocs.erase(std::find(b->allocs.begin(), b->allocs.end(), p));
+    b->bytes -= bytes ? bytes : sizeof(double);
+    HIPCHK(hipFree(p));
 }
 
 /* wave-tiled per-instance array with E elements per instance (gpu_ipm_internal.h, GArrT) */
@@ -1564,6 +1574,7 @@ try
     else if (!strcmp(f, "tau_min")) o.tau_min = *d;
     else if (!strcmp(f, "tol_comp_soft_scale")) b->tol_comp_soft_scale = *d;
     else if (!strcmp(f, "full_dense")) b->full_dense = *i != 0;
+    else if (!strcmp(f, "full_dense_slice")) b->full_dense_slice = *i < 0 ? 0 : *i;
     else if (!strcmp(f, "polish")) b->polish = *i < 0 ? 0 : (*i > 8 ? 8 : *i);
     else if (!strcmp(f, "polish_ratio")) b->polish_ratio = *d;
     else if (!strcmp(f, "polish_min")) b->polish_min = *d;
@@ -2559,8 +2570,9 @@ static int solve_epilogue(ocp_qp_gpu_batch *b)
 /*
  * FULL CONDENSING of any size (option "full_dense" = 1; FULL_CONDENSING_GPU_IPM past what one condensed stage of the stage-wise
  * families may carry): one workgroup per instance condenses every state but x0, runs the IPM on the dense problem and expands
- * (dense_kernels.hpp).  The batch is worked off in slices whose workspace stays below 8 GiB; the family's own finalize kernel
- * then recovers the multipliers of the equality-flagged rows from stationarity, as after a stage-wise solve.
+ * (dense_kernels.hpp), multipliers of the equality-flagged rows included.  The batch is worked off in slices whose workspace stays
+ * below 8 GiB (option "full_dense_slice": of that many instances); the family's own finalize kernel then sets the masked sides, as
+ * after a stage-wise solve.
  */
 static int dense_solve(ocp_qp_gpu_batch *b)
 {
@@ -2600,9 +2612,16 @@ static int dense_solve(ocp_qp_gpu_batch *b)
         S.W = o;
         b->d_kd_rows = dalloc<gqp::KdRow>(b, rows.size());
         if (!rows.empty()) HIPCHK(hipMemcpy(b->d_kd_rows, rows.data(), sizeof(gqp::KdRow) * rows.size(), hipMemcpyHostToDevice));
-        const size_t budget = (size_t) 8 << 30;
-        b->kd_slice = (int) std::max<size_t>(1, std::min<size_t>((size_t) b->B, budget / (S.W * sizeof(double))));
-        b->d_kd_ws = dalloc<double>(b, (size_t) b->kd_slice * S.W);
+    }
+    /* instances per launch: option "full_dense_slice", else what 8 GiB of workspace hold; the workspace follows a change */
+    const size_t budget = (size_t) 8 << 30;
+    const size_t fit = b->full_dense_slice > 0 ? (size_t) b->full_dense_slice : budget / (b->kd.W * sizeof(double));
+    const int slice = (int) std::max<size_t>(1, std::min<size_t>((size_t) b->B, fit));
+    if (slice != b->kd_slice)
+    {
+        if (b->d_kd_ws) dfree(b, b->d_kd_ws, sizeof(double) * (size_t) b->kd_slice * b->kd.W);
+        b->kd_slice = slice;
+        b->d_kd_ws = dalloc<double>(b, (size_t) b->kd_slice * b->kd.W);
     }
     const GqpOpts O = effective_opts(b->O, b);
     HIPCHK(hipEventRecord(b->ev0, s));
@@ -3037,6 +3056,7 @@ try
     if (!strcmp(f, "polish")) return b->polish;
     if (!strcmp(f, "full_dense")) return b->full_dense;
     if (!strcmp(f, "dense_columns")) return b->kd.nv;
+    if (!strcmp(f, "dense_slice")) return b->kd_slice;
     if (!strcmp(f, "dense_workspace_bytes")) return (double) b->kd.W * 8.0 * b->kd_slice;
     if (!strcmp(f, "polished")) return b->child && b->pcond_state == 1 && b->cond_N > 0 && b->cond_N < b->N ? b->child->n_polished : b->n_polished;
     if (!strcmp(f, "polish_reverted")) return b->child && b->pcond_state == 1 && b->cond_N > 0 && b->cond_N < b->N ? b->child->n_polish_reverted : b->n_polish_reverted;
