@@ -416,6 +416,14 @@ struct ocp_qp_gpu_batch
         int *d_oarr = nullptr, *d_oelem = nullptr, *d_ogate = nullptr, *d_ckind = nullptr, *d_celem = nullptr, *d_bad = nullptr;
         GArr cot = {nullptr, 0, 0};
         bool seeded = false; /* an adjoint seed is in the residual arrays: data_grad may run */
+        /* forward mode (k_data_tangent, tangent_build): the ops transposed into one term list per entry of the seed blob, the
+         * gates of its bound entries, the seed blob of the batch */
+        std::vector<gqp::GradOp> h_ops; /* host copy of d_ops: what tangent_build transposes */
+        bool tan_built = false;
+        int slen = 0;
+        int *d_trow = nullptr, *d_sgate = nullptr;
+        gqp::TanTerm *d_tterms = nullptr;
+        double *d_seed = nullptr;
     } grad;
 };
 
@@ -3732,6 +3740,7 @@ static void grad_build(ocp_qp_gpu_batch *b)
     G.olen = olen;
     G.lds = sizeof(double) * 2 * (size_t) olen;
     G.d_ops = upload(b, ops);
+    G.h_ops = ops;
     G.d_terms = upload(b, terms);
     G.d_oarr = upload(b, oarr); G.d_oelem = upload(b, oelem); G.d_ogate = upload(b, ogate);
     G.d_ckind = upload(b, ckind); G.d_celem = upload(b, celem);
@@ -3801,6 +3810,142 @@ try
                         G.olen, G.d_oarr, G.d_oelem, G.d_ogate, T, D.amask, D.status, per);
     HIPCHK(hipGetLastError());
     stage_out_done(b, grad, cnt, is_device);
+    return 0;
+}
+catch (const gqp_hip_failure &) { return -1; }
+
+/* ---- forward-mode data derivative (grad_kernels.hpp k_data_tangent, DESIGN.md "Data gradients", Forward mode) ----
+ * the ops of grad_build transposed: where the gradient of an input entry e reads the adjoint direction D[d], the tangent of e
+ * feeds the seed that D[d] is the derivative to -- the seed of r q zl zu b for u x sl su pi, of a bound for lam of its side
+ * (with the sign its gradient carries).  One term list per entry of the seed blob, the entry's own tangent first, then the matrix
+ * entries in blob order. */
+static void tangent_build(ocp_qp_gpu_batch *b)
+{
+    grad_build(b);
+    auto &G = b->grad;
+    if (G.tan_built) return;
+    const BulkMap &Mi = blob_map(b, BLOB_IN), &Mo = blob_map(b, BLOB_OUT), &Ms = blob_map(b, BLOB_SEED);
+    const int slen = Ms.len;
+    auto ob = [&](const char *f, int k) {
+        int l = 0;
+        const int o = f ? blob_segment(Mo, f, k, &l) : -1;
+        return l > 0 ? o : -1;
+    };
+    struct DSeed { int se; double c; };
+    std::vector<DSeed> dmap(G.olen, DSeed{-1, 0.0}); /* output-blob entry d -> the seed entry D[d] is the derivative to, its sign */
+    std::vector<std::vector<gqp::TanTerm>> lists(slen);
+    std::vector<int> sgate(slen, -1);
+    for (size_t q = 0; q < Ms.fields.size(); q++)
+    {
+        const FieldRow &r = k_fields[Ms.seg_row[q]];
+        const int k = Ms.seg_stage[q], o = Ms.seg_off[q], l = Ms.seg_len[q];
+        const FieldCtx c(b, k);
+        int li = 0, lv = 0;
+        const int oi = blob_segment(Mi, r.name, k, &li); /* the same field of the input blob */
+        const int ov = (r.flags & F_VALUE) ? blob_segment(Mi, (std::string(r.name) + "#value").c_str(), k, &lv) : -1;
+        const int oa = ob(r.ga, k), olam = ob("lam", k);
+        if (oi < 0 || li != l || (r.grad == G_VEC && oa < 0) || (r.grad == G_CT && olam < 0) || (ov >= 0 && lv != l))
+        {
+            fprintf(stderr, "\nerror: acados_amd: seed field %s of stage %d has no counterpart in the input / output blob\n", r.name, k);
+            throw gqp_hip_failure{-1};
+        }
+        for (int e = 0; e < l; e++)
+            if (r.grad == G_VEC)
+            {
+                dmap[oa + e] = DSeed{o + e, 1.0};
+                lists[o + e].push_back(gqp::TanTerm{oi + e, -1, 1.0});
+            }
+            else if (r.grad == G_CT && c.ct_eq(r, e))
+            {
+                /* an equality-flagged row: the seed of lbx is the derivative of the variable's value, the bounds take no part */
+                if (ov >= 0) lists[o + e].push_back(gqp::TanTerm{ov + e, -1, 1.0});
+                else sgate[o + e] = -2;
+            }
+            else if (r.grad == G_CT)
+            {
+                const int pos = c.ct_pos(r, e), d = c.ct_dev(pos);
+                sgate[o + e] = (k * b->fam.AW + d / 64) * 64 + d % 64;
+                dmap[olam + pos] = DSeed{o + e, -(double) r.sign};
+                lists[o + e].push_back(gqp::TanTerm{oi + e, -1, 1.0});
+            }
+    }
+    for (int e = 0; e < G.len; e++)
+    {
+        const gqp::GradOp &p = G.h_ops[e];
+        if (p.op != 2) continue;
+        /* c (D[a] - D[a2]) S[b] + c (S[a] - S[a2]) D[b], transposed */
+        auto add = [&](int d, double co, int si) {
+            if (d < 0 || dmap[d].se < 0) return;
+            lists[dmap[d].se].push_back(gqp::TanTerm{e, si, co * dmap[d].c});
+        };
+        add(p.a, p.c, p.b);
+        add(p.a2, -p.c, p.b);
+        add(p.b, p.c, p.a);
+        if (p.a2 >= 0) add(p.b, -p.c, p.a2);
+    }
+    std::vector<int> row(slen + 1, 0);
+    std::vector<gqp::TanTerm> terms;
+    for (int e = 0; e < slen; e++)
+    {
+        for (const gqp::TanTerm &t : lists[e])
+        {
+            if (t.te < 0 || t.te >= G.len || t.si >= G.olen) /* (what the kernel indexes with) */
+            {
+                fprintf(stderr, "\nerror: acados_amd: tangent table out of range at seed entry %d\n", e);
+                throw gqp_hip_failure{-1};
+            }
+            terms.push_back(t);
+        }
+        row[e + 1] = (int) terms.size();
+    }
+    G.slen = slen;
+    G.d_trow = upload(b, row); G.d_tterms = upload(b, terms); G.d_sgate = upload(b, sgate);
+    G.d_seed = dalloc<double>(b, (size_t) b->B * (size_t) std::max(slen, 1));
+    if (G.lds / 2 > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *) gqp::k_data_tangent, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (G.lds / 2)));
+    G.tan_built = true;
+}
+
+/* d(solution) along a tangent of the whole QP data: tangent in the INPUT blob layout, the result in the OUTPUT blob layout
+ * (u x sl su pi lam t), with the KKT matrix at the final iterate -- the tangent folded into one seed set on the device, then the
+ * bulk sensitivity path as it is (_sens_set_bulk on the device blob, _sens_solve, the read-back of _sens_get_bulk) */
+int ocp_qp_gpu_batch_data_jvp_bulk(ocp_qp_gpu_batch *b, const double *tangent, double *out, int is_device)
+try
+{
+    HIPCHK(hipSetDevice(b->device));
+    tangent_build(b);
+    auto &G = b->grad;
+    if (G.lds > 160 * 1024)
+    {
+        fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_data_jvp_bulk: the solution of one instance (%d doubles) does not fit the LDS of a workgroup\n", G.olen);
+        return -1;
+    }
+    G.seeded = false;      /* the residual arrays hold this call's seeds from here on: no adjoint seed survives it */
+    b->sens_open = false;  /* ... and a seed set of its own: _sens_set_bulk zeroes what an open one held */
+    const double *src = stage_in(b, tangent, (size_t) b->B * G.len, is_device);
+    gqp::GArrTable T;
+    table_fill(b, T, k_grad_arrays);
+    const int per = (b->B + GQP_GRAD_XCD - 1) / GQP_GRAD_XCD;
+    if (G.slen)
+        GQP_LAUNCH_COOP(gqp::k_data_tangent, dim3(per * GQP_GRAD_XCD), dim3(GQP_GRAD_THREADS), G.lds / 2, b->stream, G.d_seed, b->B, G.slen, src, G.len,
+                        G.d_trow, G.d_tterms, G.d_sgate, G.olen, G.d_oarr, G.d_oelem, G.d_ogate, T, b->D.amask, b->D.status, per);
+    HIPCHK(hipGetLastError());
+    if (ocp_qp_gpu_batch_sens_set_bulk(b, G.d_seed, 1)) return -1;
+    if (ocp_qp_gpu_batch_sens_solve(b)) return -1;
+    const size_t cnt = (size_t) b->B * G.olen;
+    double *dst = stage_out(b, out, cnt, is_device);
+    blob_get_out(b, dst, 1, true);
+    /* instances whose solve failed: their factor is no factor of a KKT matrix, whatever the sweeps made of a zero seed is zeroed */
+    std::vector<int> st(b->B);
+    HIPCHK(hipMemcpy(st.data(), b->D.status, sizeof(int) * b->B, hipMemcpyDeviceToHost));
+    for (int i = 0; i < b->B;)
+    {
+        int j = i;
+        while (j < b->B && st[j] != 0) j++;
+        if (j > i && G.olen) HIPCHK(hipMemsetAsync(dst + (size_t) i * G.olen, 0, sizeof(double) * (size_t) (j - i) * G.olen, b->stream));
+        i = j + 1;
+    }
+    stage_out_done(b, out, cnt, is_device);
     return 0;
 }
 catch (const gqp_hip_failure &) { return -1; }

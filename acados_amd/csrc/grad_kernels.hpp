@@ -18,6 +18,8 @@
  * traffic, the gradient blob itself (as many bytes as the input blob), is written as consecutive 8-byte words by consecutive lanes;
  * the op table (24 B per element, the same for every instance) is served by L2.  Workgroups are renumbered so that consecutive
  * instances run on the same XCD: the wave-tiled arrays of phase 1 put 16 instances into one 128-byte line, which then stays in one L2.
+ *
+ * Forward mode (k_data_tangent, below): the same tables transposed -- a tangent of the input blob folded into one seed set.
  */
 #ifndef GRAD_KERNELS_HPP_
 #define GRAD_KERNELS_HPP_
@@ -96,6 +98,62 @@ static __global__ void __launch_bounds__(GQP_GRAD_THREADS) k_data_grad(double *g
                 const GradTerm t = terms[q];
                 const double m = t.tab >= 0 ? GATL(T.a[t.tab], t.elem) : 1.0;
                 v += t.c * m * (t.d >= 0 ? D[t.d] : 1.0);
+            }
+        out[e] = v;
+    }
+}
+
+/* FORWARD MODE, the transpose of k_data_grad: a tangent of the INPUT blob, contracted with the solution, folded into one seed set
+ * (BLOB_SEED layout, natural-sign bounds: what _sens_set_bulk takes).  Entry e of the seed blob is
+ *   sum over terms q in [row[e], row[e + 1]): c_q * tangent[te_q] * (si_q >= 0 ? S[si_q] : 1)
+ * in the order of the table (host-built, gpu_batch.hip tangent_build: the ops of grad_build transposed; the same for every
+ * instance), or 0 where its gate says that the side takes no part (s_gate: as o_gate).  One workgroup per instance, numbered as in
+ * k_data_grad; phase 1 is its phase 1 without the direction; phase 2 runs the lanes along the seed entries, every lane sums its
+ * own list: no atomics, the same bits on every run.  An instance whose solve failed gets an all-zero seed row. */
+struct TanTerm
+{
+    int te, si;
+    double c;
+};
+
+static __global__ void __launch_bounds__(GQP_GRAD_THREADS) k_data_tangent(double *seed, int nb, int slen, const double *tangent, int len, const int *row,
+                                                                         const TanTerm *terms, const int *s_gate, int olen, const int *o_arr,
+                                                                         const int *o_elem, const int *o_gate, GArrTable T, GArrU64 amask,
+                                                                         const int *status, int per)
+{
+    GQP_DYN_SHARED(lds);
+    double *S = lds;
+    const int bx = blockIdx.x, tid = threadIdx.x;
+    const int i = (bx % GQP_GRAD_XCD) * per + bx / GQP_GRAD_XCD;
+    if (i >= nb) return;
+    double *out = seed + (size_t) i * (size_t) slen;
+    if (status[i] != 0)
+    {
+        for (int e = tid; e < slen; e += GQP_GRAD_THREADS) out[e] = 0.0;
+        return;
+    }
+    for (int e = tid; e < olen; e += GQP_GRAD_THREADS)
+    {
+        const int a = o_arr[e], g = o_gate[e];
+        double s = 0.0;
+        bool on = a >= 0 && g != -2;
+        if (on && g >= 0) on = (GATL(amask, g >> 6) >> (g & 63)) & 1;
+        if (on) s = GATL(T.a[a], o_elem[e]);
+        S[e] = s;
+    }
+    __syncthreads();
+    const double *tan = tangent + (size_t) i * (size_t) len;
+    for (int e = tid; e < slen; e += GQP_GRAD_THREADS)
+    {
+        const int g = s_gate[e];
+        bool on = g != -2;
+        if (on && g >= 0) on = (GATL(amask, g >> 6) >> (g & 63)) & 1;
+        double v = 0.0;
+        if (on)
+            for (int q = row[e]; q < row[e + 1]; q++)
+            {
+                const TanTerm t = terms[q];
+                v += t.c * tan[t.te] * (t.si >= 0 ? S[t.si] : 1.0);
             }
         out[e] = v;
     }

@@ -285,6 +285,25 @@ class OcpQpGpuBatch:
             grad = np.zeros((self.n_batch, self.bulk_len(0)))
         return self._blob_call(self._L.ocp_qp_gpu_batch_data_grad_bulk, grad, 0, "ocp_qp_gpu_batch_data_grad_bulk")
 
+    def data_jvp(self, tangent):
+        """forward-mode derivative of the solution along a tangent of the QP data (ocp_qp_gpu_batch_data_jvp_bulk).  tangent:
+        the input blob layout [n_batch, bulk_len(0)], NumPy or a CUDA float64 tensor (mask and index entries are ignored, Q and R
+        count with their symmetric part); returns d(solution) in the output blob layout [n_batch, bulk_len(1)] (u x sl su pi lam
+        t), of the same kind.  Instances whose last solve failed get a zero row."""
+        shape = (self.n_batch, self.bulk_len(0))
+        if hasattr(tangent, "data_ptr") and getattr(tangent, "is_cuda", False):
+            import torch
+            assert tangent.is_contiguous() and str(tangent.dtype) == "torch.float64" and tuple(tangent.shape) == shape, (tangent.shape, shape)
+            out = torch.empty((self.n_batch, self.bulk_len(1)), dtype=torch.float64, device=tangent.device)
+            rc = self._L.ocp_qp_gpu_batch_data_jvp_bulk(self._h, C.c_void_p(tangent.data_ptr()), C.c_void_p(out.data_ptr()), 1)
+        else:
+            assert tangent.flags.c_contiguous and tangent.dtype == np.float64 and tangent.shape == shape, (tangent.shape, shape)
+            out = np.zeros((self.n_batch, self.bulk_len(1)))
+            rc = self._L.ocp_qp_gpu_batch_data_jvp_bulk(self._h, tangent.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 0)
+        if rc != 0:
+            raise RuntimeError("ocp_qp_gpu_batch_data_jvp_bulk failed")
+        return out
+
     # -- KKT residuals of whatever (data, iterate) is in HBM (ocp_qp_res_compute / _nrm_inf) ----------------
     def res_compute(self):
         """residual vectors of the current iterate, one launch of a kernel independent of the IPM sweeps; read them with

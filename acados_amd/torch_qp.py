@@ -6,7 +6,9 @@
 Forward: _set_bulk (device pointer) -> solve -> _get_bulk (device pointer), nothing through the host.  Backward: one adjoint solve
 and the contraction kernel (ocp_qp_gpu_batch_adj_seed_bulk + _data_grad_bulk), gradient w.r.t. the QP data only; the cotangent may
 touch u x sl su, not pi lam t.  Q and R receive the symmetric gradient in both triangles.  Instances whose solve failed get a zero
-gradient row.  torch is imported when this module is, not by `import acados_amd`.
+gradient row.  Forward mode: under torch.autograd.forward_ad a tangent of `blob` comes out as the tangent of `sol` (u x sl su pi lam
+t; ocp_qp_gpu_batch_data_jvp_bulk: the tangent folded into one seed set and one sensitivity solve); qp_jvp is the same without a
+dual level.  torch is imported when this module is, not by `import acados_amd`.
 """
 import torch
 
@@ -24,18 +26,29 @@ class _QpSolve(torch.autograd.Function):
         gb._torch_token = token = object()
         ctx.gb, ctx.token = gb, token
         ctx.save_for_backward(blob)
+        ctx.save_for_forward(blob)
         return sol
 
     @staticmethod
-    def backward(ctx, grad_sol):
+    def _restore(ctx):
         gb = ctx.gb
         if getattr(gb, "_torch_token", None) is not ctx.token:
-            # the batch has solved other data since this forward: restore the solution the gradient belongs to
+            # the batch has solved other data since this forward: restore the solution the derivative belongs to
             (blob,) = ctx.saved_tensors
             gb.set_bulk(blob)
             gb.solve()
             gb._torch_token = ctx.token
+        return gb
+
+    @staticmethod
+    def backward(ctx, grad_sol):
+        gb = _QpSolve._restore(ctx)
         return gb.data_grad(grad_sol.detach().to(torch.float64).contiguous()), None
+
+    @staticmethod
+    def jvp(ctx, blob_t, _):
+        gb = _QpSolve._restore(ctx)
+        return gb.data_jvp(blob_t.detach().to(torch.float64).contiguous())
 
 
 def qp_solve(gb, blob):
@@ -43,6 +56,18 @@ def qp_solve(gb, blob):
     if not (blob.is_cuda and blob.dtype == torch.float64):
         raise TypeError("qp_solve: blob must be a float64 CUDA tensor")
     return _QpSolve.apply(blob, gb)
+
+
+def qp_jvp(gb, blob, tangent):
+    """d(solution) [n_batch, bulk_len(1)] of the QPs in `blob` along `tangent` (both in the input blob layout): solves `blob`,
+    then ocp_qp_gpu_batch_data_jvp_bulk; what forward_ad gives through qp_solve, without a dual level"""
+    for t in (blob, tangent):
+        if not (t.is_cuda and t.dtype == torch.float64):
+            raise TypeError("qp_jvp: blob and tangent must be float64 CUDA tensors")
+    gb.set_bulk(blob.detach().contiguous())
+    gb.solve()
+    gb._torch_token = object()
+    return gb.data_jvp(tangent.detach().contiguous())
 
 
 def blob_views(gb, blob, output=INPUT):

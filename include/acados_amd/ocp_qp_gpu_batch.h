@@ -188,6 +188,24 @@ int ocp_qp_gpu_batch_sens_get_bulk(ocp_qp_gpu_batch *b, double *blob, int is_dev
 int ocp_qp_gpu_batch_adj_seed_bulk(ocp_qp_gpu_batch *b, const double *cot, int is_device);
 int ocp_qp_gpu_batch_data_grad_bulk(ocp_qp_gpu_batch *b, double *grad, int is_device);
 
+/* Forward mode, the other half: the derivative of the solution ALONG a tangent of every entry of the QP data ("Data
+ * gradients", Forward mode).  `tangent` is in the INPUT blob layout (output = 0, one row per instance), `out` in the OUTPUT blob
+ * layout (u x sl su pi lam t): the derivative of the solution along `tangent`, taken with the KKT matrix at the final iterate, the
+ * matrix _sens_solve and _data_grad_bulk use.  One kernel folds the tangent, contracted with the solution, into one seed set
+ * (per stage, w = [u; x], s = [sl; su], lam >= 0 per side, a dot for tangent entries):
+ *   seed_r seed_q        r. q. + H. w + [B. A.]' pi + [D. C.]' (lam_ug - lam_lg)       H. = the symmetric part of the Q R entries,
+ *   seed_zl seed_zu      zl. zu. + Zl. o sl, Zu. o su                                   1/2 (Q. + Q.'), and S entry by entry
+ *   seed_b               b. + [B. A.] w
+ *   seed_lg seed_ug      the bound's tangent - [D. C.] w (both sides)
+ *   seed_lbu lbx ubu ubx lls lus   the bound's tangent (natural sign); an equality-flagged row: seed_lbx = the tangent of its
+ *                        "lbx#value" entry
+ * then _sens_set_bulk, _sens_solve and the read-back of _sens_get_bulk run as they are.  Mask and index entries, the bound entries
+ * of equality-flagged rows and of sides that do not take part contribute nothing, and the lam / t entries of `out` are 0 there.
+ * With the symmetric part, <data_grad(g), tangent> = <g, data_jvp(tangent)> holds for every tangent.  Instances whose last solve
+ * did not end with status 0 get an all-zero row.  Leaves no adjoint seed behind (a _data_grad_bulk needs a new _adj_seed_bulk).
+ * `is_device` != 0: both are device pointers.  Works wherever _sens_solve does. */
+int ocp_qp_gpu_batch_data_jvp_bulk(ocp_qp_gpu_batch *b, const double *tangent, double *out, int is_device);
+
 /* KKT residuals of an arbitrary (qp_in, qp_out): what ocp_qp_res_compute -> d_ocp_qp_res_compute and
  * ocp_qp_res_compute_nrm_inf do (acados/ocp_qp/ocp_qp_common.c:559-667; wrapper ocp_qp_inf_norm_residuals,
  * interfaces/acados_c/ocp_qp_interface.c:642-650; asserted by test/ocp_qp/test_qpsolvers.cpp:240-251).  _res_compute
