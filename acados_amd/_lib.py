@@ -75,6 +75,7 @@ def bind(L):
     L.ocp_qp_gpu_batch_sens_get_bulk.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.ocp_qp_gpu_batch_adj_seed_bulk.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.ocp_qp_gpu_batch_data_grad_bulk.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.ocp_qp_gpu_batch_adj_seed_all_bulk.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.ocp_qp_gpu_batch_data_jvp_bulk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.ocp_qp_gpu_host_alloc.argtypes = [C.c_size_t]
     L.ocp_qp_gpu_host_alloc.restype = C.c_void_p

@@ -424,6 +424,10 @@ struct ocp_qp_gpu_batch
         int *d_trow = nullptr, *d_sgate = nullptr;
         gqp::TanTerm *d_tterms = nullptr;
         double *d_seed = nullptr;
+        /* the adjoint seed of a cotangent on the whole output blob (k_adj_seed_all, seed_all_build): one entry per output entry */
+        std::vector<int> h_ckind, h_ogate; /* host copies of d_ckind / d_ogate: what seed_all_build reads */
+        bool all_built = false;
+        gqp::SeedOp *d_sops = nullptr;
     } grad;
 };
 
@@ -3744,6 +3748,7 @@ static void grad_build(ocp_qp_gpu_batch *b)
     G.d_terms = upload(b, terms);
     G.d_oarr = upload(b, oarr); G.d_oelem = upload(b, oelem); G.d_ogate = upload(b, ogate);
     G.d_ckind = upload(b, ckind); G.d_celem = upload(b, celem);
+    G.h_ckind = ckind; G.h_ogate = ogate;
     G.d_bad = dalloc<int>(b, 1);
     G.cot = garr<double>(b, (size_t) (N + 2) * n);
     if (G.lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *) gqp::k_data_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int) G.lds));
@@ -3814,6 +3819,132 @@ try
 }
 catch (const gqp_hip_failure &) { return -1; }
 
+/* output-blob entry d -> the seed entry (BLOB_SEED) that the direction D[d] of the sweeps is the derivative to, and its sign: the
+ * seed of r q zl zu b for u x sl su pi, of a bound (natural sign) for lam of its side, + for a lower and - for an upper side (the
+ * sign its gradient carries); se = -1 for t, for both sides of an equality-flagged row and for an entry without a seed.  The sweeps
+ * are symmetric under this map, so it is read in both directions: forward mode feeds the seed from the tangent of what D[d]
+ * multiplies (tangent_build), reverse mode seeds entry se with the cotangent of entry d (seed_all_build) */
+struct DSeed { int se; double c; };
+static std::vector<DSeed> seed_of_output(ocp_qp_gpu_batch *b)
+{
+    const BulkMap &Mo = blob_map(b, BLOB_OUT), &Ms = blob_map(b, BLOB_SEED);
+    std::vector<DSeed> dmap(Mo.len, DSeed{-1, 0.0});
+    for (size_t q = 0; q < Ms.fields.size(); q++)
+    {
+        const FieldRow &r = k_fields[Ms.seg_row[q]];
+        const int k = Ms.seg_stage[q], o = Ms.seg_off[q], l = Ms.seg_len[q];
+        const FieldCtx c(b, k);
+        int la = 0, ll = 0;
+        const int oa = r.ga ? blob_segment(Mo, r.ga, k, &la) : -1, olam = blob_segment(Mo, "lam", k, &ll);
+        if ((r.grad == G_VEC && (oa < 0 || la != l)) || (r.grad == G_CT && olam < 0))
+        {
+            fprintf(stderr, "\nerror: acados_amd: seed field %s of stage %d has no counterpart in the output blob\n", r.name, k);
+            throw gqp_hip_failure{-1};
+        }
+        for (int e = 0; e < l; e++)
+            if (r.grad == G_VEC)
+                dmap[oa + e] = DSeed{o + e, 1.0};
+            else if (r.grad == G_CT && !c.ct_eq(r, e))
+            {
+                const int pos = c.ct_pos(r, e);
+                if (pos >= ll)
+                {
+                    fprintf(stderr, "\nerror: acados_amd: seed field %s of stage %d lies outside lam of the output blob\n", r.name, k);
+                    throw gqp_hip_failure{-1};
+                }
+                dmap[olam + pos] = DSeed{o + e, -(double) r.sign};
+            }
+    }
+    return dmap;
+}
+
+/* the table of k_adj_seed_all: where the cotangent of every output entry goes (seed_of_output for the seed entry, the seed blob's
+ * own map for its residual array, element and stored sign) */
+static void seed_all_build(ocp_qp_gpu_batch *b)
+{
+    grad_build(b);
+    auto &G = b->grad;
+    if (G.all_built) return;
+    const BulkMap &Mo = blob_map(b, BLOB_OUT), &Ms = blob_map(b, BLOB_SEED);
+    const std::vector<DSeed> dmap = seed_of_output(b);
+    std::vector<int> ssgn(Ms.len, 1); /* the sign a seed entry is stored with (what blob_map uploaded as d_sgn) */
+    for (size_t q = 0; q < Ms.fields.size(); q++)
+        for (int e = 0; e < Ms.seg_len[q]; e++) ssgn[Ms.seg_off[q] + e] = k_fields[Ms.seg_row[q]].sign;
+    std::vector<gqp::SeedOp> ops(G.olen, gqp::SeedOp{-1, 0, -1, -1, 0, 0, 0.0});
+    for (size_t q = 0; q < Mo.fields.size(); q++)
+    {
+        const Arr arr = k_fields[Mo.seg_row[q]].arr;
+        const int k = Mo.seg_stage[q], o = Mo.seg_off[q], l = Mo.seg_len[q];
+        int lt = 0;
+        const int ot = arr == ARR_lam ? blob_segment(Mo, "t", k, &lt) : -1; /* the partner of a lam entry: t of the same side */
+        if (arr == ARR_t) continue;                                        /* (consumed by its lam entry) */
+        for (int e = 0; e < l; e++)
+        {
+            const int d = o + e;
+            gqp::SeedOp &p = ops[d];
+            if (arr == ARR_ux) p.cot = G.h_ckind[d] ? Mo.elem[d] : -1; /* kinds 1 and 3: the fixed variables' own term of op 3 */
+            const int se = dmap[d].se;
+            if (G.h_ckind[d] == 3 || G.h_ogate[d] == -2 || se < 0 || Ms.arr[se] < 0) continue;
+            p.slot = Ms.arr[se];
+            p.dst = Ms.elem[se];
+            p.c = dmap[d].c * ssgn[se];
+            if (arr != ARR_lam) continue;
+            p.gate = G.h_ogate[d];
+            p.le = Mo.elem[d];
+            p.part = ot + e;
+            if (ot < 0 || lt != l || p.gate < 0)
+            {
+                fprintf(stderr, "\nerror: acados_amd: lam of stage %d has no t / no activity bit in the output blob\n", k);
+                throw gqp_hip_failure{-1};
+            }
+        }
+    }
+    /* (what the kernel indexes with) */
+    const GArr dst[] = {b->D.rg, b->D.rgs, b->D.rb, b->D.rd};
+    for (int d = 0; d < G.olen; d++)
+    {
+        const gqp::SeedOp &p = ops[d];
+        const bool lamrow = p.slot >= 0 && p.gate >= 0;
+        if (p.slot >= 4 || (p.slot >= 0 && (p.dst < 0 || p.dst >= dst[p.slot].E)) || p.cot >= G.cot.E ||
+            (lamrow && (p.le < 0 || p.le >= b->D.lam.E || p.le >= b->D.t.E || p.part < 0 || p.part >= G.olen || (p.gate >> 6) >= b->D.amask.E)))
+        {
+            fprintf(stderr, "\nerror: acados_amd: adjoint seed table out of range at output entry %d\n", d);
+            throw gqp_hip_failure{-1};
+        }
+    }
+    G.d_sops = upload(b, ops);
+    G.all_built = true;
+}
+
+/* _adj_seed_bulk for a cotangent on every entry of the output blob: the same sequence, k_adj_seed_all in place of k_adj_seed; refuses
+ * nothing.  _data_grad_bulk follows it as it is: its contraction holds for any right-hand side of the symmetric system */
+int ocp_qp_gpu_batch_adj_seed_all_bulk(ocp_qp_gpu_batch *b, const double *cot, int is_device)
+try
+{
+    HIPCHK(hipSetDevice(b->device));
+    seed_all_build(b);
+    auto &G = b->grad;
+    if (G.lds > 160 * 1024)
+    {
+        fprintf(stderr, "acados_amd: ocp_qp_gpu_batch_adj_seed_all_bulk: the solution of one instance (%d doubles) does not fit the LDS of a workgroup\n", G.olen);
+        return -1;
+    }
+    G.seeded = false;
+    if (sens_begin(b)) return -1; /* zeroes the seed arrays, factorises at the solution where the sweeps run in place */
+    const double *src = stage_in(b, cot, (size_t) b->B * G.olen, is_device);
+    HIPCHK(hipMemsetAsync(G.cot.p, 0, sizeof(double) * (size_t) G.cot.E * b->Bp, b->stream));
+    gqp::GArrTable T;
+    table_fill(b, T, k_seed_arrays);
+    if (G.olen)
+        hipLaunchKernelGGL(gqp::k_adj_seed_all, dim3((G.olen + 255) / 256, b->B), dim3(256), 0, b->stream, src, b->B, G.olen, G.d_sops, T, G.cot,
+                           b->D.lam, b->D.t, b->D.amask, b->D.status);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->stream));
+    G.seeded = true;
+    return 0;
+}
+catch (const gqp_hip_failure &) { return -1; }
+
 /* ---- forward-mode data derivative (grad_kernels.hpp k_data_tangent, DESIGN.md "Data gradients", Forward mode) ----
  * the ops of grad_build transposed: where the gradient of an input entry e reads the adjoint direction D[d], the tangent of e
  * feeds the seed that D[d] is the derivative to -- the seed of r q zl zu b for u x sl su pi, of a bound for lam of its side
@@ -3824,15 +3955,9 @@ static void tangent_build(ocp_qp_gpu_batch *b)
     grad_build(b);
     auto &G = b->grad;
     if (G.tan_built) return;
-    const BulkMap &Mi = blob_map(b, BLOB_IN), &Mo = blob_map(b, BLOB_OUT), &Ms = blob_map(b, BLOB_SEED);
+    const BulkMap &Mi = blob_map(b, BLOB_IN), &Ms = blob_map(b, BLOB_SEED);
     const int slen = Ms.len;
-    auto ob = [&](const char *f, int k) {
-        int l = 0;
-        const int o = f ? blob_segment(Mo, f, k, &l) : -1;
-        return l > 0 ? o : -1;
-    };
-    struct DSeed { int se; double c; };
-    std::vector<DSeed> dmap(G.olen, DSeed{-1, 0.0}); /* output-blob entry d -> the seed entry D[d] is the derivative to, its sign */
+    const std::vector<DSeed> dmap = seed_of_output(b);
     std::vector<std::vector<gqp::TanTerm>> lists(slen);
     std::vector<int> sgate(slen, -1);
     for (size_t q = 0; q < Ms.fields.size(); q++)
@@ -3843,18 +3968,14 @@ static void tangent_build(ocp_qp_gpu_batch *b)
         int li = 0, lv = 0;
         const int oi = blob_segment(Mi, r.name, k, &li); /* the same field of the input blob */
         const int ov = (r.flags & F_VALUE) ? blob_segment(Mi, (std::string(r.name) + "#value").c_str(), k, &lv) : -1;
-        const int oa = ob(r.ga, k), olam = ob("lam", k);
-        if (oi < 0 || li != l || (r.grad == G_VEC && oa < 0) || (r.grad == G_CT && olam < 0) || (ov >= 0 && lv != l))
+        if (oi < 0 || li != l || (ov >= 0 && lv != l))
         {
-            fprintf(stderr, "\nerror: acados_amd: seed field %s of stage %d has no counterpart in the input / output blob\n", r.name, k);
+            fprintf(stderr, "\nerror: acados_amd: seed field %s of stage %d has no counterpart in the input blob\n", r.name, k);
             throw gqp_hip_failure{-1};
         }
         for (int e = 0; e < l; e++)
             if (r.grad == G_VEC)
-            {
-                dmap[oa + e] = DSeed{o + e, 1.0};
                 lists[o + e].push_back(gqp::TanTerm{oi + e, -1, 1.0});
-            }
             else if (r.grad == G_CT && c.ct_eq(r, e))
             {
                 /* an equality-flagged row: the seed of lbx is the derivative of the variable's value, the bounds take no part */
@@ -3863,9 +3984,8 @@ static void tangent_build(ocp_qp_gpu_batch *b)
             }
             else if (r.grad == G_CT)
             {
-                const int pos = c.ct_pos(r, e), d = c.ct_dev(pos);
+                const int d = c.ct_dev(c.ct_pos(r, e));
                 sgate[o + e] = (k * b->fam.AW + d / 64) * 64 + d % 64;
-                dmap[olam + pos] = DSeed{o + e, -(double) r.sign};
                 lists[o + e].push_back(gqp::TanTerm{oi + e, -1, 1.0});
             }
     }

@@ -20,6 +20,9 @@
  * instances run on the same XCD: the wave-tiled arrays of phase 1 put 16 instances into one 128-byte line, which then stays in one L2.
  *
  * Forward mode (k_data_tangent, below): the same tables transposed -- a tangent of the input blob folded into one seed set.
+ *
+ * The seed of the adjoint sweeps: k_adj_seed for a cotangent on u x sl su (it refuses one on pi lam t), k_adj_seed_all for a
+ * cotangent on every entry of the output blob; k_data_grad follows either.
  */
 #ifndef GRAD_KERNELS_HPP_
 #define GRAD_KERNELS_HPP_
@@ -178,6 +181,46 @@ static __global__ void __launch_bounds__(256) k_adj_seed(const double *blob, int
     if (kd == 2) { GATL(rgs, c_elem[e]) = v; return; }
     GATL(cot, c_elem[e]) = v;
     if (kd == 1) GATL(rg, c_elem[e]) = v;
+}
+
+/* the cotangent of the WHOLE output blob as seed of the adjoint sweeps (the transpose of the read-back of k_data_tangent's solve):
+ * entry e goes, times c, to element dst of the seed array `slot` of T (the table of _sens_set_bulk: rg rgs rb rd; -1: to none) and,
+ * as it is, to element cot of the cotangent copy (u x; -1: no copy).  The table (host-built, gpu_batch.hip seed_all_build) is the
+ * same for every instance:
+ *   u x        rg, and the copy; a fixed variable: the copy only (its row takes no seed)
+ *   sl su      rgs
+ *   pi         rb of the dynamics it is the multiplier of
+ *   lam        rd of its side, where the side takes part (gate: activity bit stage_word * 64 + bit; an equality-flagged row has
+ *              slot -1), with the cotangent of t folded in: lam dt + t dlam = 0 along every direction of the sweeps, so
+ *              <g_lam, dlam> + <g_t, dt> = <g_lam - (t / lam) g_t, dlam>.  g_t is entry `part` of the same row, lam and t are
+ *              element le of the batch's arrays; where lam is not > 0 the t term is dropped
+ *   t          nothing: its lam lane consumes it
+ * One writer per destination, plain stores; an instance whose solve failed writes nothing (its seeds stay 0).
+ * Grid (elements / 256, instances): consecutive lanes read consecutive words of the instance's row. */
+struct SeedOp
+{
+    int slot, dst, cot, gate, le, part;
+    double c;
+};
+
+static __global__ void __launch_bounds__(256) k_adj_seed_all(const double *blob, int nb, int len, const SeedOp *ops, GArrTable T, GArr cot, GArr lam,
+                                                             GArr t, GArrU64 amask, const int *status)
+{
+    const int i = blockIdx.y, e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb || e >= len || status[i] != 0) return;
+    const SeedOp o = ops[e];
+    if (o.slot < 0 && o.cot < 0) return;
+    const double *row = blob + (size_t) i * len;
+    double v = row[e];
+    if (o.cot >= 0) GATL(cot, o.cot) = v;
+    if (o.slot < 0) return;
+    if (o.gate >= 0)
+    {
+        if (!((GATL(amask, o.gate >> 6) >> (o.gate & 63)) & 1)) return;
+        const double l = GATL(lam, o.le);
+        if (l > 0.0) v -= GATL(t, o.le) / l * row[o.part];
+    }
+    GATL(T.a[o.slot], o.dst) = o.c * v;
 }
 
 } // namespace gqp

@@ -277,7 +277,20 @@ class OcpQpGpuBatch:
         dL/d(solution) in the output blob layout [n_batch, bulk_len(1)] (u x sl su used; pi lam t must be zero), NumPy or a
         CUDA float64 tensor; returns dL/d(data) in the input blob layout [n_batch, bulk_len(0)], of the same kind.  Q and R carry
         the symmetric gradient in both triangles; instances whose last solve failed get a zero row."""
-        self._blob_call(self._L.ocp_qp_gpu_batch_adj_seed_bulk, cot, 1, "ocp_qp_gpu_batch_adj_seed_bulk")
+        return self._adjoint(self._L.ocp_qp_gpu_batch_adj_seed_bulk, cot, "ocp_qp_gpu_batch_adj_seed_bulk")
+
+    def data_vjp(self, cot):
+        """data_grad for a cotangent on EVERY entry of the output blob, pi lam t included (ocp_qp_gpu_batch_adj_seed_all_bulk +
+        _data_grad_bulk): the transpose of data_jvp on the whole output blob.  data_vjp(g) is the input-blob row v with
+        <v, t> = <g, data_jvp(t)> for every tangent t; cot and the result as in data_grad.  Inherited from data_jvp: Q and R carry
+        the symmetric G in both triangles; masks and index entries get 0; lam and t cotangents of sides outside the activity mask
+        and of equality-flagged rows are ignored; an instance whose solve failed gets a zero row; the KKT matrix is the one at the
+        final iterate.  The identity holds to the noise of d lam on active sides (eps lam / t, tenfold per digit of the solve
+        tolerance: DESIGN.md 4.8); on a cotangent that is zero on pi lam t the result is bit for bit that of data_grad."""
+        return self._adjoint(self._L.ocp_qp_gpu_batch_adj_seed_all_bulk, cot, "ocp_qp_gpu_batch_adj_seed_all_bulk")
+
+    def _adjoint(self, seed_fn, cot, what):
+        self._blob_call(seed_fn, cot, 1, what)
         if hasattr(cot, "data_ptr") and getattr(cot, "is_cuda", False):
             import torch
             grad = torch.empty((self.n_batch, self.bulk_len(0)), dtype=torch.float64, device=cot.device)

@@ -4,9 +4,10 @@
     loss(sol).backward()            # blob.grad: dL/d(blob), same shape as blob
 
 Forward: _set_bulk (device pointer) -> solve -> _get_bulk (device pointer), nothing through the host.  Backward: one adjoint solve
-and the contraction kernel (ocp_qp_gpu_batch_adj_seed_bulk + _data_grad_bulk), gradient w.r.t. the QP data only; the cotangent may
-touch u x sl su, not pi lam t.  Q and R receive the symmetric gradient in both triangles.  Instances whose solve failed get a zero
-gradient row.  Forward mode: under torch.autograd.forward_ad a tangent of `blob` comes out as the tangent of `sol` (u x sl su pi lam
+and the contraction kernel (OcpQpGpuBatch.data_vjp: ocp_qp_gpu_batch_adj_seed_all_bulk + _data_grad_bulk), gradient w.r.t. the QP
+data only; the cotangent may touch every entry of the solution, u x sl su pi lam t (one on t is folded into lam of its side; those on
+lam and t of sides that take no part are ignored).  Q and R receive the symmetric gradient in both triangles.  Instances whose solve
+failed get a zero gradient row.  Forward mode: under torch.autograd.forward_ad a tangent of `blob` comes out as the tangent of `sol` (u x sl su pi lam
 t; ocp_qp_gpu_batch_data_jvp_bulk: the tangent folded into one seed set and one sensitivity solve); qp_jvp is the same without a
 dual level.  torch is imported when this module is, not by `import acados_amd`.
 """
@@ -43,7 +44,7 @@ class _QpSolve(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_sol):
         gb = _QpSolve._restore(ctx)
-        return gb.data_grad(grad_sol.detach().to(torch.float64).contiguous()), None
+        return gb.data_vjp(grad_sol.detach().to(torch.float64).contiguous()), None
 
     @staticmethod
     def jvp(ctx, blob_t, _):

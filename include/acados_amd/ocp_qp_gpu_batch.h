@@ -188,6 +188,18 @@ int ocp_qp_gpu_batch_sens_get_bulk(ocp_qp_gpu_batch *b, double *blob, int is_dev
 int ocp_qp_gpu_batch_adj_seed_bulk(ocp_qp_gpu_batch *b, const double *cot, int is_device);
 int ocp_qp_gpu_batch_data_grad_bulk(ocp_qp_gpu_batch *b, double *grad, int is_device);
 
+/* _adj_seed_bulk for a cotangent on EVERY entry of the output blob (u x sl su pi lam t): refuses nothing, and _data_grad_bulk follows
+ * it as it follows _adj_seed_bulk.  The pair computes data_vjp(g), the transpose of _data_jvp_bulk (below) on the whole output blob:
+ * the input-blob row v with <v, tangent> = <g, data_jvp(tangent)> for every tangent.  It inherits from _data_jvp_bulk: Q and R carry
+ * the symmetric G in both triangles; masks and index entries get 0; the lam and t cotangents of sides outside the activity mask and of
+ * equality-flagged rows are ignored; an instance whose solve failed gets a zero row; the KKT matrix is the one at the final iterate.
+ * A cotangent on t is folded into the one on lam of its side, g_lam - (t / lam) g_t with lam and t at the final iterate (the sweeps
+ * return lam dt + t dlam = 0 on every side that takes part), a cotangent on pi seeds the dynamics residual, one on lam the bound of
+ * its side.  The identity holds to the noise of d lam = -(lam / t) dt on active sides, eps lam / t, which grows tenfold with every
+ * digit of the solve tolerance ("Cotangents on the multipliers").  On a cotangent that is zero on pi lam t the result
+ * is bit for bit that of _adj_seed_bulk. */
+int ocp_qp_gpu_batch_adj_seed_all_bulk(ocp_qp_gpu_batch *b, const double *cot, int is_device);
+
 /* Forward mode, the other half: the derivative of the solution ALONG a tangent of every entry of the QP data ("Data
  * gradients", Forward mode).  `tangent` is in the INPUT blob layout (output = 0, one row per instance), `out` in the OUTPUT blob
  * layout (u x sl su pi lam t): the derivative of the solution along `tangent`, taken with the KKT matrix at the final iterate, the

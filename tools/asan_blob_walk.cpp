@@ -196,6 +196,16 @@ int main()
         double mx = 0.0;
         for (double v : grad) { CHECK(v == v); mx = v > mx ? v : (-v > mx ? -v : mx); }
         CHECK(mx > 0.0);
+        /* ... and with a cotangent on every entry of the output blob: seed_all_build walks the seed map and the output map */
+        std::vector<double> all((size_t) B * n_out), grad_all((size_t) B * n_in, 0.0);
+        for (double &v : all) v = rnd();
+        CHECK(ocp_qp_gpu_batch_adj_seed_all_bulk(b, all.data(), 0) == 0);
+        CHECK(ocp_qp_gpu_batch_data_grad_bulk(b, grad_all.data(), 0) == 0);
+        for (double v : grad_all) CHECK(v == v);
+        CHECK(memcmp(grad_all.data(), grad.data(), sizeof(double) * grad.size()) != 0);
+        CHECK(ocp_qp_gpu_batch_adj_seed_all_bulk(b, cot.data(), 0) == 0);
+        CHECK(ocp_qp_gpu_batch_data_grad_bulk(b, grad_all.data(), 0) == 0);
+        CHECK(memcmp(grad_all.data(), grad.data(), sizeof(double) * grad.size()) == 0); /* zero on pi lam t: the bits of _adj_seed_bulk */
     }
     CHECK(ocp_qp_gpu_batch_get_scalar(b, "time_pack") >= 0.0);
     ocp_qp_gpu_batch_destroy(b);

@@ -4,6 +4,8 @@
   seed         _adj_seed_bulk (cotangent scatter; the factorisation at the solution where the sweeps run in place)
   sweeps       _sens_set_bulk + _sens_solve with an all-zero seed: the adjoint sweeps alone (sliced on this family)
   grad_total   _data_grad_bulk: sweeps + contraction
+  seed_all     _adj_seed_all_bulk with a cotangent on every entry of the output blob (u x sl su pi lam t), grad_total_all the
+               _data_grad_bulk behind it
   contraction  grad_total - sweeps; GB/s = gradient bytes written / contraction time
     python tools/data_grad_rate.py [batch] [out.json]"""
 import ctypes as C
@@ -34,6 +36,7 @@ def main():
     for k in range(N + 1):
         o, n = gb.bulk_offset(1, "x", k)
         cot[:, o:o + n] = 1.0
+    cot_all = torch.randn((B, lout), dtype=torch.float64, device="cuda")
     grad = torch.empty((B, lin), dtype=torch.float64, device="cuda")
     zseed = torch.zeros((B, lseed), dtype=torch.float64, device="cuda")
     torch.cuda.synchronize()
@@ -47,7 +50,7 @@ def main():
         assert rc == 0 or rc is None, rc
         return e0.elapsed_time(e1)
 
-    res = {k: [] for k in ("solve", "seed", "sweeps", "grad_total")}
+    res = {k: [] for k in ("solve", "seed", "sweeps", "grad_total", "seed_all", "grad_total_all")}
     p = lambda t: C.c_void_p(t.data_ptr())
     gb.solve()   # warm-up: module load, sub-batches
     for _ in range(REPS):
@@ -55,6 +58,8 @@ def main():
         res["sweeps"].append(timed(lambda: L.ocp_qp_gpu_batch_sens_set_bulk(gb._h, p(zseed), 1) or L.ocp_qp_gpu_batch_sens_solve(gb._h)))
         res["seed"].append(timed(lambda: L.ocp_qp_gpu_batch_adj_seed_bulk(gb._h, p(cot), 1)))
         res["grad_total"].append(timed(lambda: L.ocp_qp_gpu_batch_data_grad_bulk(gb._h, p(grad), 1)))
+        res["seed_all"].append(timed(lambda: L.ocp_qp_gpu_batch_adj_seed_all_bulk(gb._h, p(cot_all), 1)))
+        res["grad_total_all"].append(timed(lambda: L.ocp_qp_gpu_batch_data_grad_bulk(gb._h, p(grad), 1)))
     ms = {k: float(np.median(v)) for k, v in res.items()}
     contraction = max(ms["grad_total"] - ms["sweeps"], 1e-6)
     row = {"shape": "C2", "N": N, "batch": B, "kernel": gb.kernel_name, "ms": ms, "contraction_ms": contraction,
